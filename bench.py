@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Throughput of the AuctionGym hot path on MI355X: auctions resolved per second.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N ... bench.py --gpus N     (one process per GPU)
+
+A plain run sets up, warms up, times the K steps of the headline workload below, writes the
+last step's outputs if --dump-outputs is given, and prints the result line. --full adds every
+other line: the headline's generate mode, configs[1..4] with their learner updates, the P = 8
+variants and the CPU baselines.
 
 Workload (north star "SP_Oracle-shaped batches"): the SP_Oracle.json
 population -- 6 agents with OracleAllocator + TruthfulBidder, 12 items, E = 5, P = 2
@@ -14,7 +19,8 @@ auction index) and resident in HBM before timing. One step = one fused pass
 per-auction / per-participant output in SoA form; with N > 1 the per-agent counters are
 then summed across GPUs (int64 all-reduce over RCCL: the only collective of the path).
 
-Printed: one JSON line (rank 0). `roofline.achieved` = algorithmic bytes per launch
+Printed: one JSON line (rank 0); the lines of --full are further objects in it.
+`roofline.achieved` = algorithmic bytes per launch
 (140 B per auction: SURVEY §8d's 141 with winner and outcome as one 4-B word) / average ag_simulate duration from HIP events on the
 launch stream. `cpu_baseline` = the oracle (the C restatement of the reference path,
 kind "port") timed on host cores on a bounded sample of the same inputs.
@@ -226,6 +232,31 @@ def measured_copy_peak(nbytes=1 << 32, reps=20):
     ms = a.elapsed_time(b) / reps
     del src, dst
     return 2 * nbytes / (ms * 1e-3) / 1e9
+
+
+DUMP_SAMPLE = 1 << 18  # auctions written by --dump-outputs (25 MB of .npy files)
+
+
+def dump_outputs(path, eng, out, cnt):
+    """--dump-outputs: what the last timed step left in the arrays a caller of ag_simulate
+    receives, as path/<field>.npy: winner, outcome and item in float32 (small integers), price
+    and the per-slot bid, est_ctr, true_ctr, best_ev ([P][n]) in float64, of every auction of the
+    step or, above DUMP_SAMPLE auctions, of a fixed sample of them (indices drawn from numpy's
+    default_rng(0), ascending, in index.npy); the per-agent counters whole (counters.npy: float64
+    [N][C]; counter_limbs.npy: their exact fixed-point limbs, each below 2^53)."""
+    from auctiongym_amd.engine import unpack_outputs
+    os.makedirs(path, exist_ok=True)
+    B = out["price"].shape[0]
+    idx = np.arange(B) if B <= DUMP_SAMPLE else np.unique(np.random.default_rng(0).integers(0, B, DUMP_SAMPLE))
+    sel = torch.from_numpy(idx).to(out["price"].device)
+    o = unpack_outputs({k: t.index_select(t.dim() - 1, sel) for k, t in out.items()})
+    o.pop("winner_outcome", None)
+    np.save(os.path.join(path, "index.npy"), idx.astype(np.float64))
+    for k, t in o.items():
+        np.save(os.path.join(path, k + ".npy"),
+                t.cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32))
+    np.save(os.path.join(path, "counters.npy"), eng.counters_to_numpy(cnt))
+    np.save(os.path.join(path, "counter_limbs.npy"), cnt.cpu().numpy().astype(np.float64))
 
 
 def cpu_baseline(items, values, inp, sample, threads, min_seconds=10.0, max_passes=40):
@@ -743,6 +774,13 @@ def main():
                     help="auctions per GPU per step (2^27: 19 GB of inputs + outputs resident in HBM; a "
                          "step of ~3.5 ms keeps the driver's few warm-up steps past the clock ramp of a "
                          "fresh process, DESIGN.md section 6)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also run every other line: its generate mode, "
+                         "configs[1..4] with the learners' updates, the P = 8 variants, the CPU baselines "
+                         "(the --no-* / --populations / --p8-only options below choose among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (its output arrays, sampled above "
+                         f"{DUMP_SAMPLE} auctions, and the counters) as DIR/<name>.npy (rank 0's shard)")
     ap.add_argument("--no-generate", action="store_true", help="skip the generate-mode lines")
     ap.add_argument("--peak-last", action="store_true",
                     help="measure the copy peak after the timed steps (A/B of the clock warm-up; default: before)")
@@ -768,6 +806,8 @@ def main():
                          "(shards, counter all-reduce, agent-parallel updates) where only one GPU is at hand; "
                          "its timings mean nothing")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline's timed steps alone
+        args.no_generate = args.no_ts = args.no_populations = args.no_p8 = args.no_cpu_baseline = True
     global LEARNER_PARALLEL, GENERATE_LINES
     LEARNER_PARALLEL = args.learner_parallel
     GENERATE_LINES = not args.no_generate
@@ -852,8 +892,11 @@ def main():
     bpa = algorithmic_bytes_per_auction(E, P, first_price=False, packed_winner=True)
     achieved = bpa * B / (kern_ms * 1e-3) / 1e9
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, out, cnt)
+
     gen = None
-    if not args.no_generate:
+    if GENERATE_LINES:
         # generate mode: the same workload with the inputs drawn inside the
         # kernel (ag_simulate_generated: the bits ag_generate wrote), writes only
         def gstep(i=None):

@@ -273,7 +273,13 @@ def capture(cfg, rounds, torch_seed=0, keep=False):
 
 
 def save_capture(name, arrays, agg, meta):
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **arrays)
+    path = os.path.join(OUT, name + ".npz")
+    np.savez_compressed(path, **arrays)
+    if os.path.getsize(path) > 1 << 20 and "ts_noise" in arrays:
+        # no fixture above 1 MiB: the Thompson noise goes into a file of its own
+        # (conftest.load_capture puts the two together)
+        np.savez_compressed(path, **{k: v for k, v in arrays.items() if k != "ts_noise"})
+        np.savez_compressed(os.path.join(OUT, name + ".ts_noise.npz"), ts_noise=arrays["ts_noise"])
     with open(os.path.join(OUT, name + ".json"), "w") as f:
         json.dump({"meta": meta, "aggregates": agg}, f, indent=1)
     print("wrote", name, {k: v.shape for k, v in arrays.items()})

@@ -89,7 +89,7 @@ def test_bench_multi_rank_rehearsal(gpu, tmp_path):
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", str(1 << 20), "--ts-batch", str(1 << 16),
+           "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", str(1 << 20), "--ts-batch", str(1 << 16),
            "--no-cpu-baseline", "--no-generate", "--populations", "configs_4", "--rehearse-on-one-gpu"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]

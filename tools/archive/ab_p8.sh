@@ -12,7 +12,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 LIB=auction-gym_amd/auctiongym_amd/libauctiongym_hip.so
 KEY=${KEY:-configs_4:8}
-POP="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-ts --no-update --no-generate --batch 1048576 ${POPARGS:---populations configs_4 --p8-only}"
+POP="python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-ts --no-update --no-generate --batch 1048576 ${POPARGS:---populations configs_4 --p8-only}"
 if [ -n "${VARIANTS-base8 pk8}" ]; then
   timeout -k 10 400 python -u tools/ab_pop.py $KEY ${VARIANTS-base8 pk8} > "$OUT/ab_${KEY/:/_}.log" 2>&1 || { echo "ab rc=$?"; exit 1; }
   tail -n 8 "$OUT/ab_${KEY/:/_}.log"

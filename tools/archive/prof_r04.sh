@@ -11,9 +11,9 @@ TAG=${TAG:-r04p}
 OUT=gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-HEAD="python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-ts --no-populations --no-generate"
-ts() { echo "python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-update --no-populations --no-generate --batch 1048576 ${1:---no-p8}"; }
-pop() { echo "python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-ts --no-update --no-generate --batch 1048576 --populations $1 ${2:---no-p8}"; }
+HEAD="python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-ts --no-populations --no-generate"
+ts() { echo "python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-update --no-populations --no-generate --batch 1048576 ${1:---no-p8}"; }
+pop() { echo "python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-ts --no-update --no-generate --batch 1048576 --populations $1 ${2:---no-p8}"; }
 HK='k_oracle<2, 6, false>'
 GK='k_simulate'
 SQA="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM"
@@ -22,7 +22,7 @@ step() { local name=$1 secs=$2; shift 2; echo "== $name"; timeout -k 10 "$secs" 
 pmc() { local name=$1 k=$2; shift 2; local ctr=$1; shift; step "$name" 150 rocprofv3 --pmc $ctr --kernel-include-regex "$k" --output-format csv -d "$OUT/$name" -o run -- "$@"; }
 for s in ${STEPS:-bench head pops sq stats}; do
   case $s in
-    bench) step bench_driver 400 python bench.py --steps 20 --warmup 5 ;;
+    bench) step bench_driver 400 python bench.py --full --steps 20 --warmup 5 ;;
     head)
       pmc fetch "$HK" FETCH_SIZE $HEAD && pmc write "$HK" WRITE_SIZE $HEAD &&
       pmc sqA "$HK" "$SQA" $HEAD && pmc sqB "$HK" "$SQB" $HEAD ;;
@@ -48,7 +48,7 @@ for s in ${STEPS:-bench head pops sq stats}; do
       T1="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64"
       T2="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_LDS SQ_INSTS_SMEM SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE"
       eval "CTR=\$${s#trainer_}"
-      UPD="python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-ts --no-generate --no-p8 --batch 1048576 --populations configs_2"
+      UPD="python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-ts --no-generate --no-p8 --batch 1048576 --populations configs_2"
       echo "== $s"
       timeout -k 10 300 rocprofv3 --pmc $CTR --kernel-include-regex "k_bidder_train|k_lrts_train" --output-format csv -d "$OUT/$s" -o run -- $UPD > "$OUT/$s.log" 2>&1
       echo "rc=$?"
@@ -62,7 +62,7 @@ for s in ${STEPS:-bench head pops sq stats}; do
         pmc "hd_$c" "$HK" "${c}_sum" $HEAD && pmc "c4p8_$c" "$GK" "${c}_sum" $(pop configs_4 --p8-only) &&
         pmc "c1_$c" "$GK" "${c}_sum" $(ts) || exit 1
       done ;;
-    stats) step kernel_stats 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline ;;
+    stats) step kernel_stats 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline ;;
   esac
 done
 echo "== done"

@@ -13,9 +13,9 @@ TAG=${TAG:-r06x}
 OUT=gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-HEAD="python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-ts --no-populations --no-generate"
-ts() { echo "python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-update --no-populations --no-generate --batch 1048576 ${1:---no-p8}"; }
-pop() { echo "python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-ts --no-update --no-generate --batch 1048576 --populations $1 ${2:---no-p8}"; }
+HEAD="python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-ts --no-populations --no-generate"
+ts() { echo "python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-update --no-populations --no-generate --batch 1048576 ${1:---no-p8}"; }
+pop() { echo "python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-ts --no-update --no-generate --batch 1048576 --populations $1 ${2:---no-p8}"; }
 HK='k_oracle<2, 6, false>'
 GK='k_simulate'
 SQA="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM"
@@ -26,18 +26,18 @@ pmc() { local name=$1 k=$2; shift 2; local ctr=$1; shift; step "$name" 150 rocpr
 trace() { local wl=$1; shift; step "tr_$wl" 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/tr_$wl" -o run -- "$@"; }
 for s in ${STEPS:-bench trace head pops sq}; do
   case $s in
-    bench) step bench_driver 400 python bench.py --steps 20 --warmup 5 ;;
+    bench) step bench_driver 400 python bench.py --full --steps 20 --warmup 5 ;;
     trace)
       # the headline and its generate mode at the driver's shape; each population line with its
       # generate-mode line, no learner update (the update's cooperative launches are traced in
       # the `update` step, last: rocprofv3 has faulted at exit after them)
-      trace hd python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-ts --no-populations --no-p8 &&
-      trace c1 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-update --no-populations --no-p8 --batch 1048576 &&
-      trace c1p8 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-update --no-populations --p8-only --batch 1048576 &&
+      trace hd python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-ts --no-populations --no-p8 &&
+      trace c1 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-update --no-populations --no-p8 --batch 1048576 &&
+      trace c1p8 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-update --no-populations --p8-only --batch 1048576 &&
       for c in 2 3 4; do
-        trace c$c python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-ts --no-update --no-p8 --batch 1048576 --populations configs_$c || exit 1
+        trace c$c python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-ts --no-update --no-p8 --batch 1048576 --populations configs_$c || exit 1
       done &&
-      trace c4p8 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-ts --no-update --p8-only --batch 1048576 --populations configs_4 ;;
+      trace c4p8 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-ts --no-update --p8-only --batch 1048576 --populations configs_4 ;;
     head)
       pmc hd_fetch "$HK" FETCH_SIZE $HEAD && pmc hd_write "$HK" WRITE_SIZE $HEAD &&
       pmc hd_sqA "$HK" "$SQA" $HEAD && pmc hd_sqB "$HK" "$SQB" $HEAD ;;
@@ -54,11 +54,11 @@ for s in ${STEPS:-bench trace head pops sq}; do
         pmc c${c}_sqA "$GK" "$SQA" $(pop configs_$c) && pmc c${c}_sqB "$GK" "$SQB" $(pop configs_$c) || exit 1
       done ;;
     gen)  # the generate-mode kernels' instruction mix (VALU-bound: Philox)
-      GEN1="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-update --no-populations --no-p8 --batch 1048576"
+      GEN1="python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-update --no-populations --no-p8 --batch 1048576"
       pmc c1g_sqA "k_simulate.*true>" "$SQA" $GEN1 && pmc c1g_sqB "k_simulate.*true>" "$SQB" $GEN1 ;;
     update)  # LAST in a call (see above): the learners' update of configs_2 under the trace
       echo "== update"
-      timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/tr_update" -o run -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-ts --no-generate --no-p8 --batch 1048576 --populations configs_2 > "$OUT/tr_update.log" 2>&1
+      timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/tr_update" -o run -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-ts --no-generate --no-p8 --batch 1048576 --populations configs_2 > "$OUT/tr_update.log" 2>&1
       echo "rc=$?"
       break ;;
   esac
