@@ -31,6 +31,19 @@ from .replay import draw_round, draw_round_population, draw_rounds_native, draw_
 C = _agent_mod.C
 
 
+def warn_unpinned_catalogue(K, D, stacklevel=2):
+    """Warn where the catalogue shape (K items, D = E + 1) is one whose true CTRs are not pinned
+    bit for bit to the reference's."""
+    if K == 1 or (D >= 8 and K % 4 != 0):
+        # the true CTRs restate numpy's items @ context in OpenBLAS dgemv_t's order, which
+        # tests/test_oracle_golden.py and tests/test_oracle_shapes.py pin for K >= 2 with D <= 7
+        # or K % 4 == 0; for other shapes numpy runs other kernels (ddot for K = 1,
+        # CPU-dependent remainder kernels)
+        warnings.warn(f"catalogue shape K={K}, E+1={D}: bit-exact parity of the true CTRs with the "
+                      "reference's numpy dot is unpinned for this shape (DESIGN.md section 5)",
+                      stacklevel=stacklevel)
+
+
 class Auction:
     """Base class for auctions (src/Auction.py:9-26)."""
 
@@ -58,12 +71,7 @@ class Auction:
         K = int(self._num_items.max())
         N = len(agents)
         D = embedding_size + 1
-        if K == 1 or (D >= 8 and K % 4 != 0):
-            # the true CTRs restate numpy's items @ context in OpenBLAS dgemv_t's order, which
-            # tests/test_oracle_golden.py pins for K >= 2 with D <= 7 or K % 4 == 0; for other
-            # shapes numpy runs other kernels (ddot for K = 1, CPU-dependent remainder kernels)
-            warnings.warn(f"catalogue shape K={K}, E+1={D}: bit-exact parity of the true CTRs with the "
-                          "reference's numpy dot is unpinned for this shape (DESIGN.md section 5)", stacklevel=2)
+        warn_unpinned_catalogue(K, D, stacklevel=3)
         for a in agents:
             if a.allocator.kind is None or a.bidder.kind is None:
                 raise NotImplementedError(

@@ -7,9 +7,13 @@ there too, and its update (src/BidderAllocation.py:29-65) is the GPU training ke
 ag_lrts_update, batched over every LR-TS agent of the auction (Agent.update). The model
 tensors here are host mirrors of the device posterior, refreshed after each update.
 """
+import warnings
+
 import torch
 
 from . import _lib
+
+_warned_widths = set()  # LR-TS model widths already warned about (once per width)
 
 
 class Allocator:
@@ -70,6 +74,13 @@ class PyTorchLogisticRegressionAllocator(Allocator):
         # an Auction defers this allocator's update to train it together with the other LR-TS
         # agents' (Auction._settle_lrts); reading the posterior or the epochs runs it first
         self._settle = None
+        if embedding_size + 1 != 5 and embedding_size + 1 not in _warned_widths:
+            # the estimated CTRs restate torch's CPU F.linear (sgemv) summation order, which
+            # tests/test_oracle_golden.py pins for the model width 5 (obs_embedding_size = 4)
+            _warned_widths.add(embedding_size + 1)
+            warnings.warn(f"LR-TS model width OE+1={embedding_size + 1}: bit-exact parity of the estimated CTRs "
+                          "with the reference's torch sgemv is unpinned for this width (DESIGN.md section 5)",
+                          stacklevel=2)
         self.response_model = PyTorchLogisticRegression(n_dim=embedding_size, n_items=num_items)
         self.thompson_sampling = thompson_sampling
         self.embedding_size = embedding_size

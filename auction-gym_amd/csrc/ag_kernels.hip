@@ -559,6 +559,13 @@ int simulate_general(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch
     W = 1;
     k = pick_kernel(s.num_participants, D, prune, W, gmode | ship | genb, bt);
   }
+  // 1024-lane workgroups asked for by option where no such build exists (they come with the
+  // screened item search, P <= kMaxP): an error, not a quiet 256-lane launch
+  if (!k && !gen && c->general && c->block_threads == kLargeThreads)
+    return ag_set_error(AG_ERR_UNSUPPORTED,
+                        "ag_simulate: AG_OPT_SIM_BLOCK_THREADS = %d needs the screened item search (K <= %d, positive "
+                        "catalogue values, E+1 <= 8) and P <= %d (P=%d D=%d K=%d)",
+                        kLargeThreads, 2 * kMaxKPairs, kMaxP, s.num_participants, D, s.num_items);
   if (!k && bt != kThreads) {
     bt = kThreads;
     k = pick_kernel(s.num_participants, D, prune, W, gmode | ship | genb, bt);
@@ -1007,8 +1014,14 @@ int ag_simulate_generated(ag_ctx *c, uint64_t seed, uint64_t first, int64_t B, a
     if (c->vl_any_search)
       return ag_set_error(AG_ERR_UNSUPPORTED, "ag_simulate_generated: ValueLearningBidders bidding by search "
                                               "(their 128-point grids are not drawn in the kernel)");
-    if (c->shape.num_participants > 64)
-      return ag_set_error(AG_ERR_UNSUPPORTED, "ag_simulate_generated: P > 64");
+    if (!c->can_simulate)
+      return ag_set_error(AG_ERR_UNSUPPORTED,
+                          "ag_simulate_generated: supports E+1 in {2..9,11,13,16} (E+1 <= 8 when P > %d) and a "
+                          "catalogue that fits LDS (P=%d, D=%d, N=%d, K=%d)",
+                          kMaxP, s.num_participants, c->D, s.num_agents, s.num_items);
+    if (s.num_participants > kMaxP)  // no generate-mode build of the runtime-P kernel
+      return ag_set_error(AG_ERR_UNSUPPORTED, "ag_simulate_generated: general populations need P <= %d (P=%d)",
+                          kMaxP, s.num_participants);
     AgDeviceGuard g(c->device);
     return simulate_general(c, B, nullptr, out, counters_fx, (hipStream_t)stream, true, seed, first);
   }

@@ -240,7 +240,8 @@ typedef enum ag_option {
   AG_OPT_SIM_BLOCK_THREADS = 9,   /* value: lanes per workgroup of the general simulate kernel:
                                      0 = auto (1024 when the population's LDS would keep fewer than
                                      16 waves resident per CU with 256-lane workgroups), 256 or
-                                     1024; identical results */
+                                     1024; identical results. 1024 exists with the screened item
+                                     search and P <= 8 only: elsewhere ag_simulate refuses it */
   AG_OPT_SIM_GENERAL_MODE = 10,   /* value: 0 = auto (TruthfulBidder-only populations run the
                                      general kernel built without the bid-shading code: fewer
                                      VGPRs), 1 = always the full general build; identical results */

@@ -1102,15 +1102,42 @@ def mixed_ts_flags_capture(out_name="sp_ts_mixed_flags_r2048", rounds=2048):
     save_capture(out_name, a, g, m)
 
 
+def shape_captures():
+    """Captures off the catalogue shape (K = 12, E = 5, OE = 4): the tables of tests/shape_cases.py
+    -- Oracle + truthful populations through oracle_truthful_cfg, LR-TS / shading populations from
+    the reference's own configs with embedding_size, obs_embedding_size, the agents' num_items and
+    the allocator's kwargs (embedding_size = OE, num_items = K) set. The config travels in the
+    fixture's meta."""
+    sys.path.insert(0, os.path.dirname(OUT))
+    import shape_cases as S
+    for name, (N, K, E, OE, P, alloc, seed) in {**S.ORACLE_PINNED, **S.ORACLE_UNPINNED}.items():
+        cfg = oracle_truthful_cfg(N, K, P, alloc, seed=seed, E=E, OE=OE)
+        a, g, m = capture(cfg, S.ROUNDS)
+        m["config"] = cfg
+        save_capture(name, a, g, m)
+    for name, (cfg_name, K, E, OE) in {**S.POP_PINNED, **S.POP_UNPINNED}.items():
+        cfg = load_cfg(cfg_name, embedding_size=E, obs_embedding_size=OE)
+        for ag in cfg["agents"]:
+            ag["num_items"] = K
+            ag["allocator"]["kwargs"] = dict(ag["allocator"]["kwargs"], embedding_size=OE, num_items=K)
+        cfg["output_dir"] = "/tmp/ag_golden_unused/"
+        a, g, m = capture(cfg, S.ROUNDS)
+        m["config"] = cfg
+        save_capture(name, a, g, m)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--full", action="store_true", help="also run SP_Oracle as shipped (3x20x10k rounds, ~1 min)")
     ap.add_argument("--which", choices=["dm", "ips", "dr", "dmo", "search"], help="with --only learners/drivers: one config")
     ap.add_argument("--only", choices=["empirical", "csv", "dr", "learners", "drivers", "memory", "later", "mixedts", "ragged",
-                                       "interleave"],
+                                       "interleave", "shapes"],
                     help="regenerate one fixture family only")
     args = ap.parse_args()
     install_shims()
+    if args.only == "shapes":
+        shape_captures()
+        return
     if args.only == "interleave":
         interleave_kat()
         return
