@@ -9,6 +9,20 @@
 // the reference's early stop) runs on the device. Sums over the agent's records are exact
 // (fixed-point terms added as integers), so the result is independent of record order and
 // lane assignment; the arithmetic is oracle/ag_oracle_dr.c ora_dr_update, bit for bit.
+//
+// Three kernels drive the same fits and give the same models bit for bit (tests/test_gpu_rp.py):
+//   k_bidder_train<PH>  persistent, a group of workgroups per learner, the fits as loops
+//                       (fit_winrate, fit_imitation, fit_dr, fit_dm, fit_pl): ag_bidder_update;
+//   k_bidder_epoch      one launch per epoch, the learner's state (FitSt) in HBM: the record-
+//                       parallel multi-GPU update, the drop-in update's noise windows;
+//   k_bidder_pipe<PH>   persistent, every learner in every workgroup, FitSt in LDS:
+//                       ag_bidder_rp_run, AG_BIDDER_PIPE=1.
+// What they share stands once: the per-record terms (wr_pair, imit_rec, dr_rec, dm_rec), the
+// hyper-parameters (fit_hyper), a workgroup's slice of the records (wg_slice), the estimated
+// utilities (estimated_utilities), the words per fit and the trace rows (fit_words, trace_row);
+// the last two kernels also the FitSt machine (fit_enter, fit_after, fit_step) and a
+// workgroup's sums of an epoch (epoch_partial). On the host, block_tables lays out the
+// workgroups and barrier lines of ag_bidder_update's and ag_bidder_rp_begin's launches.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -38,18 +52,6 @@ constexpr int kDrThreads = 256;
 constexpr int kWrEpochs = 32768, kInitEpochs = 16384, kDrEpochs = 32768;
 constexpr int64_t kBidderChunk = 8192;  // records per workgroup of a PolicyLearningBidder (default)
 constexpr int64_t kMinChunk = 1024;     // fewest records per workgroup of an exact-sum learner's split
-#ifndef AG_DR_ABLATE_XCHG
-#define AG_DR_ABLATE_XCHG 0  // diagnostic (wrong fits by design): each workgroup steps on its own partial sums
-#endif
-#ifndef AG_DR_WR_RECS
-#define AG_DR_WR_RECS 1  // records per iteration of the win-rate loop (2: wr_pair2; A/B)
-#endif
-#ifndef AG_DR_SLOW_OUTLINE
-#define AG_DR_SLOW_OUTLINE 0  // 1: the win-rate rows' rare path out of line (wr_slow; A/B)
-#endif
-#ifndef AG_DR_SHARED_DIV
-#define AG_DR_SHARED_DIV 1  // the win-rate row's two divisions by 1 + e share one reciprocal (ag_div.h)
-#endif
 #ifndef AG_DR_REC_LDS0
 #define AG_DR_REC_LDS0 (32 * 1024)
 #endif
@@ -198,6 +200,48 @@ __device__ __forceinline__ bool stop_step(Stopper &s, int epoch, float loss) {
   return epoch - s.best_epoch > s.wait;
 }
 
+// The exact-sum learners' fits in the reference's order (src/Bidder.py:229-325, :500-615): the
+// ValueLearningBidder's win count, the win-rate fit, DoublyRobustBidder's estimated utilities
+// (no fit: one pass), the imitation of the logging policy, the policy fit (DR or DM).
+enum { kFitWins = 0, kFitWr, kFitEu, kFitInit, kFitPol, kFitDone };
+// the row of a fit in epochs [3] and traces [3][kDrEpochs]: win-rate, imitation, policy fit
+__device__ __forceinline__ int fit_slot(int fit) { return fit == kFitWr ? 0 : (fit == kFitInit ? 1 : 2); }
+__device__ __forceinline__ float *trace_row(float *traces, int a, int fit) {
+  return traces + ((size_t)a * 3 + fit_slot(fit)) * kDrEpochs;
+}
+// words (hi, lo pairs) of a fit's per-epoch sums: the win count, the win-rate fit's loss and 4
+// gradient terms, the 12-parameter fits' 16 sums
+__device__ __forceinline__ constexpr int fit_words(int fit) {
+  return fit == kFitWins ? 2 : (fit == kFitWr ? 10 : 32);
+}
+
+// A fit's hyper-parameters, by fit and bidder kind -- the one statement of them, read by the
+// persistent fits (fit_winrate, fit_imitation, fit_dr, fit_dm) and by the FitSt machine:
+// Adam(lr, weight decay, AMSGrad), ReduceLROnPlateau(threshold, factor, min_lr, patience; none
+// for the imitation), early stop after `wait` epochs without a 1e-6 improvement, <= max_epochs.
+//   win-rate (src/Bidder.py:229-252 ValueLearningBidder, :500-530 DoublyRobustBidder)
+//   imitation (src/Models.py:106-137), any bidder kind
+//   policy fit: DR (src/Bidder.py:562-590), DM (ValueLearningBidder 'policy', :258-303)
+struct FitHyper {
+  double lr;
+  float wd;
+  double threshold, factor, min_lr;
+  int patience, wait, max_epochs;
+};
+__device__ __forceinline__ constexpr FitHyper fit_hyper(int fit, int bk) {
+  const bool dr = bk == AG_BIDDER_DOUBLY_ROBUST;
+  if (fit == kFitWr)
+    return dr ? FitHyper{3e-3, (float)1e-6, 1e-4, 0.2, 1e-7, 256, 1024, kWrEpochs}
+              : FitHyper{3e-3, (float)1e-6, 1e-4, 0.1, 1e-7, 100, 512, kWrEpochs};
+  if (fit == kFitInit) return FitHyper{1e-3, (float)1e-4, 0.0, 0.0, 0.0, 0, 512, kInitEpochs};
+  return dr ? FitHyper{7e-3, (float)1e-4, 5e-3, 0.2, 1e-8, 100, 512, kDrEpochs}
+            : FitHyper{2e-3, (float)1e-6, 1e-4, 0.1, 1e-7, 100, 256, kInitEpochs};
+}
+__device__ __forceinline__ Plateau plateau_of(const FitHyper &H) {
+  return Plateau{INFINITY, H.threshold, H.factor, H.min_lr, 0, H.patience};
+}
+__device__ __forceinline__ Stopper stopper_of(const FitHyper &H) { return Stopper{INFINITY, -1, H.wait}; }
+
 // forward values of the policy; eh / eam / eas = exp of h / am / as, kept for the backward
 // pass's softplus derivatives
 struct PolF {
@@ -218,28 +262,18 @@ __device__ __forceinline__ void policy_fwd(const float *p, double c, double v, P
 }
 // softplus through the main paths alone (ok cleared when an input leaves them); r = the
 // reciprocal of 1 + e, shared by log1p's c / (1 + e) and the backward pass's e / (e + 1)
-// (AG_DR_SHARED_DIV; where ok holds and u <= 20, e is in [2^-29, 2^29]: div_safe's range)
+// (ag_div.h; where ok holds and u <= 20, e is in [2^-29, 2^29]: div_safe's range)
 __device__ __forceinline__ double softplus_main(double u, double &e, double &r, const uint64_t *tab, bool &ok) {
   e = agexp::exp_main(u, tab);
   bool lok;
-#if AG_DR_SHARED_DIV
   r = agdiv::recip(1.0 + e);
   const double l = aglog1p::log1p_main_t(e, lok, SharedDiv{r});
-#else
-  r = 0.0;
-  const double l = aglog1p::log1p_main(e, lok);
-#endif
   ok = (int)ok & (int)agexp::exp_in_main(u) & ((int)lok | (int)(u > 20.0));
   return u > 20.0 ? u : l;
 }
 // dsoftplus_e from softplus_main's reciprocal (the same bits where its ok holds)
 __device__ __forceinline__ double dsoftplus_r(double u, double e, double r) {
-#if AG_DR_SHARED_DIV
   return u > 20.0 ? 1.0 : agdiv::div_core(e, e + 1.0, r);
-#else
-  (void)r;
-  return dsoftplus_e(u, e);
-#endif
 }
 // policy_fwd through the main paths alone: true when they gave policy_fwd's values (every
 // softplus input inside them), else the caller runs policy_fwd -- one rare branch per record
@@ -381,7 +415,7 @@ struct Coop {
 template <int NV>
 __device__ __forceinline__ void exact_totals(const int64_t (&acc)[NV], TrainLds &S, Coop &C) {
   block_sums<NV>(acc, S.w, S.tot);
-  if (C.nblk > 1 && !(AG_DR_ABLATE_XCHG & 1)) {
+  if (C.nblk > 1) {
 #if AG_COOP_GROUPED
     agcoop::agent_allreduce_grouped(C.gcnt, C.acc, 32, C.rank, C.nblk, S.tot, 2 * NV, S.tot, ++C.rnd, S.gprev);
 #else
@@ -482,6 +516,12 @@ __device__ __forceinline__ double fit_eps(const FitNoise &F, int e, int64_t i) {
 struct Chunk {
   int64_t c0, nb, n;
 };
+// workgroup `rank` of the G that share an agent's n records: a contiguous slice each
+__device__ __forceinline__ Chunk wg_slice(int64_t n, int G, int rank) {
+  const int64_t per = (n + G - 1) / G;
+  const int64_t c0 = (int64_t)rank * per < n ? (int64_t)rank * per : n;
+  return Chunk{c0, (c0 + per < n ? c0 + per : n) - c0, n};
+}
 
 // The workgroup's records as the fits read them, every epoch: the first `cap` of its chunk
 // staged once in LDS as float32 fields (every fit consumes them through a float32 rounding,
@@ -563,14 +603,9 @@ __device__ __forceinline__ WrMain wr_main(double c, double v, double g, double y
   bool lok;
   // p's division and log1p's c / u both divide by 1 + e: one reciprocal (ag_div.h; on the main
   // paths e >= exp(-512), c is 0 or >= 2^-81 in magnitude, |f| >= 2^-53: div_safe's range)
-#if AG_DR_SHARED_DIV
   const double d1 = 1.0 + m.e, r1 = agdiv::recip(d1);
   m.Lz = aglog1p::log1p_main_t(m.e, lok, SharedDiv{r1});
   m.pw = agdiv::div_core(m.z >= 0.0 ? 1.0 : m.e, d1, r1);
-#else
-  m.Lz = aglog1p::log1p_main(m.e, lok);
-  m.pw = (m.z >= 0.0 ? 1.0 : m.e) / (1.0 + m.e);
-#endif
   m.u = y > 0.0 ? -m.z : m.z;
   m.t = fmin(m.u > 20.0 ? m.u : (m.u > 0.0 ? m.a + m.Lz : m.Lz), 100.0);
   m.gz = m.pw - y;
@@ -607,33 +642,6 @@ __device__ __forceinline__ void wr_finish(int64_t (&acc)[5], WrMain m, double c,
   if (!aug) addw(acc[3], t3);  // the augmentation row's g = 0 term is +-0: rounds to 0
   addw(acc[4], fxb_fast(m.gz));
 }
-__device__ __forceinline__ void wr_row(int64_t (&acc)[5], double c, double v, double g, double y, bool aug,
-                                       double w0, double w1, double w2, double w3, const uint64_t *tab) {
-  wr_finish(acc, wr_main(c, v, g, y, aug, w0, w1, w2, w3, tab), c, v, g, y, aug, tab);
-}
-// the rare path of a row, out of line (the main path keeps its registers): the row from the
-// full exp / log1p and the general fixed-point conversion -- the same terms wr_finish adds
-struct WrTerms {
-  int64_t t[5];
-};
-__device__ __noinline__ WrTerms wr_slow(double c, double v, double g, double y, bool aug, double w0, double w1,
-                                        double w2, double w3, const uint64_t *tab) {
-  const double z = c * w0 + v * w1 + g * w2 + w3;
-  const double a = __builtin_fabs(z);
-  const double e = agexp::exp(-a, tab);
-  const double Lz = aglog1p::log1p(e);
-  const double pw = (z >= 0.0 ? 1.0 : e) / (1.0 + e);
-  const double u = y > 0.0 ? -z : z;
-  const double t = fmin(u > 20.0 ? u : (u > 0.0 ? a + Lz : Lz), 100.0);
-  const double gz = pw - y;
-  WrTerms r;
-  r.t[0] = fxb(t);
-  r.t[1] = fxb(gz * c);
-  r.t[2] = fxb(gz * v);
-  r.t[3] = aug ? 0 : fxb(gz * g);
-  r.t[4] = fxb(gz);
-  return r;
-}
 
 // a record's logged row and its gamma = 0, y = 0 augmentation row, both main paths first
 __device__ __forceinline__ void wr_pair(int64_t (&acc)[5], double c, double v, double g, double y, double w0,
@@ -651,61 +659,12 @@ __device__ __forceinline__ void wr_pair(int64_t (&acc)[5], double c, double v, d
     addw(acc[2], fxb_x(B.x2));
     addw(acc[4], fxb_fast(B.gz));
   } else {
-#if AG_DR_SLOW_OUTLINE
-    const WrTerms ta = wr_slow(c, v, g, y, false, w0, w1, w2, w3, tab);
-    const WrTerms tb = wr_slow(c, v, 0.0, 0.0, true, w0, w1, w2, w3, tab);
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      addw(acc[k], ta.t[k]);
-      if (k != 3) addw(acc[k], tb.t[k]);
-    }
-#else
     wr_finish(acc, A, c, v, g, y, false, tab);
     wr_finish(acc, B, c, v, 0.0, 0.0, true, tab);
-#endif
-  }
-}
-// two records' four rows, main paths first, one rare branch (AG_DR_WR_RECS = 2)
-__device__ __forceinline__ void wr_pair2(int64_t (&acc)[5], double c0, double v0, double g0, double y0, double c1,
-                                         double v1, double g1, double y1, double w0, double w1, double w2, double w3,
-                                         const uint64_t *tab) {
-  const WrMain A0 = wr_main(c0, v0, g0, y0, false, w0, w1, w2, w3, tab);
-  const WrMain B0 = wr_main(c0, v0, 0.0, 0.0, true, w0, w1, w2, w3, tab);
-  const WrMain A1 = wr_main(c1, v1, g1, y1, false, w0, w1, w2, w3, tab);
-  const WrMain B1 = wr_main(c1, v1, 0.0, 0.0, true, w0, w1, w2, w3, tab);
-  if (__builtin_expect((int)A0.ok & (int)B0.ok & (int)A1.ok & (int)B1.ok, 1)) {
-    addw(acc[0], fxb_fast(A0.t));
-    addw(acc[1], fxb_fast(A0.gz * c0));
-    addw(acc[2], fxb_x(A0.x2));
-    addw(acc[3], fxb_x(A0.x3));
-    addw(acc[4], fxb_fast(A0.gz));
-    addw(acc[0], fxb_fast(B0.t));
-    addw(acc[1], fxb_fast(B0.gz * c0));
-    addw(acc[2], fxb_x(B0.x2));
-    addw(acc[4], fxb_fast(B0.gz));
-    addw(acc[0], fxb_fast(A1.t));
-    addw(acc[1], fxb_fast(A1.gz * c1));
-    addw(acc[2], fxb_x(A1.x2));
-    addw(acc[3], fxb_x(A1.x3));
-    addw(acc[4], fxb_fast(A1.gz));
-    addw(acc[0], fxb_fast(B1.t));
-    addw(acc[1], fxb_fast(B1.gz * c1));
-    addw(acc[2], fxb_x(B1.x2));
-    addw(acc[4], fxb_fast(B1.gz));
-  } else {
-    const WrTerms t[4] = {wr_slow(c0, v0, g0, y0, false, w0, w1, w2, w3, tab),
-                          wr_slow(c0, v0, 0.0, 0.0, true, w0, w1, w2, w3, tab),
-                          wr_slow(c1, v1, g1, y1, false, w0, w1, w2, w3, tab),
-                          wr_slow(c1, v1, 0.0, 0.0, true, w0, w1, w2, w3, tab)};
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int k = 0; k < 5; ++k)
-        if (k != 3 || (r & 1) == 0) addw(acc[k], t[r].t[k]);
   }
 }
 
-// a lane that ran wr_row for nrec records (both rows each): its accumulators unbiased
+// a lane that ran wr_pair for nrec records (both rows each): its accumulators unbiased
 __device__ __forceinline__ void wr_unbias(int64_t (&acc)[5], int64_t nrec) {
   fx_unbias(acc[0], 2 * nrec);
   fx_unbias(acc[1], 2 * nrec);
@@ -715,57 +674,35 @@ __device__ __forceinline__ void wr_unbias(int64_t (&acc)[5], int64_t nrec) {
 }
 
 // PyTorchWinRateEstimator fit (src/Bidder.py:229-252 ValueLearningBidder, :500-530
-// DoublyRobustBidder): BCE (mean) over the logs plus the gamma = 0, y = 0 augmentation,
-// Adam(lr 3e-3, wd 1e-6, AMSGrad), ReduceLROnPlateau(patience, factor, min_lr 1e-7),
-// early stop after `wait` epochs without a 1e-6 improvement, <= 32768 epochs.
-__device__ int fit_winrate(const RecView &V, const Chunk &K, TrainLds &S, Coop &C, int patience, double factor,
-                           int wait, const double *adam_tab, float *tr) {
+// DoublyRobustBidder): BCE (mean) over the logs plus the gamma = 0, y = 0 augmentation;
+// H = fit_hyper(kFitWr, the bidder's kind).
+__device__ int fit_winrate(const RecView &V, const Chunk &K, TrainLds &S, Coop &C, const FitHyper H,
+                           const double *adam_tab, float *tr) {
   const int tid = threadIdx.x;
   adam_reset(S);
-  double lr = 3e-3;
-  Plateau pl{INFINITY, 1e-4, factor, 1e-7, 0, patience};
-  Stopper sp{INFINITY, -1, wait};
+  double lr = H.lr;
+  Plateau pl = plateau_of(H);
+  Stopper sp = stopper_of(H);
   const double M = 2.0 * (double)K.n;
   int e = 0;
-  for (; e < kWrEpochs; ++e) {
+  for (; e < H.max_epochs; ++e) {
     int64_t acc[5] = {0, 0, 0, 0, 0};
     const double w0 = (double)S.wr[0], w1 = (double)S.wr[1], w2 = (double)S.wr[2], w3 = (double)S.wr[3];
     // record j's logged row and its gamma = 0, y = 0 augmentation row together (two
     // independent chains for the scheduler; the sums are exact, so any order)
     int64_t nrec = 0;
-#if AG_DR_WR_RECS == 2
-    if (!(AG_DR_ABLATE_XCHG & 2)) {  // two staged records per iteration, then as each_record
-      const int64_t ns = K.nb < V.cap ? K.nb : V.cap;
-      int64_t j = tid;
-      for (; j + kDrThreads < ns; j += 2 * kDrThreads) {
-        const int64_t k = j + kDrThreads;
-        wr_pair2(acc, V.template ctr_<true>(j), V.template val_<true>(j), V.template gam_<true>(j),
-                 V.template won_<true>(j), V.template ctr_<true>(k), V.template val_<true>(k),
-                 V.template gam_<true>(k), V.template won_<true>(k), w0, w1, w2, w3, S.tab);
-        nrec += 2;
-      }
-      for (; j < ns; j += kDrThreads, ++nrec)
-        wr_pair(acc, V.template ctr_<true>(j), V.template val_<true>(j), V.template gam_<true>(j),
-                V.template won_<true>(j), w0, w1, w2, w3, S.tab);
-      for (; j < K.nb; j += kDrThreads, ++nrec)
-        wr_pair(acc, V.template ctr_<false>(j), V.template val_<false>(j), V.template gam_<false>(j),
-                V.template won_<false>(j), w0, w1, w2, w3, S.tab);
-    }
-#else
-    if (!(AG_DR_ABLATE_XCHG & 2))  // diagnostic: 2 = no records (the epoch's fixed cost alone)
     each_record(V, K.nb, [&](int64_t j, auto L) {
       constexpr bool l = decltype(L)::value;
       const double c = V.template ctr_<l>(j), v = V.template val_<l>(j);
       wr_pair(acc, c, v, V.template gam_<l>(j), V.template won_<l>(j), w0, w1, w2, w3, S.tab);
       ++nrec;
     });
-#endif
     wr_unbias(acc, nrec);
     exact_totals<5>(acc, S, C);
     // every thread: the same loss; threads 0..3 step their parameter
     const float loss = (float)(fxv(S.tot[0], S.tot[1]) / M);
     const float g = tid < 4 ? (float)(fxv(S.tot[2 + 2 * tid], S.tot[3 + 2 * tid]) / M) : 0.0f;
-    adam_step_block(S, S.wr, 4, g, e, lr, (float)1e-6, adam_tab);
+    adam_step_block(S, S.wr, 4, g, e, lr, H.wd, adam_tab);
     if (tid == 0 && tr) tr[e] = loss;
     plateau_step(pl, loss, lr);  // every thread keeps the same scheduler state
     const bool stop = stop_step(sp, e, loss);
@@ -807,15 +744,16 @@ __device__ __forceinline__ void imit_rec(int64_t (&acc)[16], const float *pol, d
 
 // BidShadingContextualBandit.initialise_policy (src/Models.py:106-137): imitation of the
 // logging policy, MSE of mu to the logged gammas + MSE of softplus(sigma) (without
-// min_sigma) to 0.05; Adam(lr 1e-3, wd 1e-4, AMSGrad), early stop after 512 epochs.
+// min_sigma) to 0.05; fit_hyper(kFitInit): no scheduler.
 __device__ int fit_imitation(const RecView &V, const Chunk &K, TrainLds &S, Coop &C, const double *adam_tab,
                              float *tr) {
+  constexpr FitHyper H = fit_hyper(kFitInit, AG_BIDDER_DOUBLY_ROBUST);  // (the same for every kind)
   const int tid = threadIdx.x;
   adam_reset(S);
-  Stopper sp{INFINITY, -1, 512};
+  Stopper sp = stopper_of(H);
   const double n = (double)K.n;
   int e = 0;
-  for (; e < kInitEpochs; ++e) {
+  for (; e < H.max_epochs; ++e) {
     int64_t acc[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) acc[j] = 0;
@@ -829,7 +767,7 @@ __device__ int fit_imitation(const RecView &V, const Chunk &K, TrainLds &S, Coop
     exact_totals<16>(acc, S, C);
     const float loss = (float)(fxv(S.tot[24], S.tot[25]) / n + fxv(S.tot[26], S.tot[27]) / n);
     const float g = tid < 12 ? (float)(fxv(S.tot[2 * tid], S.tot[2 * tid + 1]) / n) : 0.0f;
-    adam_step_block(S, S.pol, 12, g, e, 1e-3, (float)1e-4, adam_tab);
+    adam_step_block(S, S.pol, 12, g, e, H.lr, H.wd, adam_tab);
     if (tid == 0 && tr) tr[e] = loss;
     const bool stop = stop_step(sp, e, loss);
     __syncthreads();
@@ -877,7 +815,6 @@ __device__ __forceinline__ void dr_rec(int64_t (&acc)[16], const float *pol, con
   bool ok = policy_fwd_main(pol, c, v, f, tab);
   const double mu = f.mu, sg = f.sigma;
   const double p0 = (double)fmaxf(prop, 1e-15f);
-#if AG_DR_SHARED_DIV
   // three divisions by sg, two by p0: one reciprocal each (ag_div.h; a record whose operands
   // leave div_safe's range takes dr_rec_exact)
   const double rsg = agdiv::recip(sg), rp0 = agdiv::recip(p0);
@@ -889,13 +826,6 @@ __device__ __forceinline__ void dr_rec(int64_t (&acc)[16], const float *pol, con
   const double iw = agdiv::div_core(pi, p0, rp0);
   ok = (int)ok & (int)agdiv::div_safe(mu - g, sg) & (int)agdiv::div_safe(ex, sg) & (int)agdiv::div_safe(pi, p0) &
        (int)agdiv::div_safe(du, p0);
-#else
-  const double zz = (mu - g) / sg;
-  const double xp = -(zz * zz) / 2.0;
-  const double pdf_raw = agexp::exp_main(xp, tab) / sg * inv_sqrt2pi;
-  const double pi = pdf_raw < 1e-30 ? 1e-30 : pdf_raw;
-  const double iw = pi / p0;
-#endif
   const double iwc = iw < 1.0 / 50.0 ? 1.0 / 50.0 : (iw > 50.0 ? 50.0 : iw);
   const double raw = mu + sg * ep;
   const double gs = raw < 0.0 ? 0.0 : (raw > 1.0 ? 1.0 : raw);
@@ -907,15 +837,9 @@ __device__ __forceinline__ void dr_rec(int64_t (&acc)[16], const float *pol, con
   d[12] = -(du * iwc + Wv * (V - V * gs));
   double dpi_dmu = 0.0, dpi_dsg = 0.0;
   if (pdf_raw >= 1e-30 && iw >= 1.0 / 50.0 && iw <= 50.0) {
-#if AG_DR_SHARED_DIV
     const double k = agdiv::div_core(du, p0, rp0);
     dpi_dmu = k * pdf_raw * (g - mu) / (sg * sg);
     dpi_dsg = k * pdf_raw * ((g - mu) * (g - mu) / (sg * sg * sg) - agdiv::div_core(1.0, sg, rsg));
-#else
-    const double k = du / p0;
-    dpi_dmu = k * pdf_raw * (g - mu) / (sg * sg);
-    dpi_dsg = k * pdf_raw * ((g - mu) * (g - mu) / (sg * sg * sg) - 1.0 / sg);
-#endif
   }
   double ddm = 0.0;
   if (raw >= 0.0 && raw <= 1.0) ddm = -Wv * V + (V - V * gs) * Wv * (1.0 - Wv) * (double)wr[2];
@@ -930,18 +854,18 @@ __device__ __forceinline__ void dr_rec(int64_t (&acc)[16], const float *pol, con
 
 // DoublyRobustBidder's policy fit (src/Bidder.py:562-590, src/Models.py:201-218): loss
 // -mean((u - u^) clip(pi / pi0, 1/50, 50) + W(ctr, value, g~) (V - V g~)), g~ = clip(mu +
-// sigma eps, 0, 1); Adam(lr 7e-3, wd 1e-4, AMSGrad), ReduceLROnPlateau(patience 100, factor
-// 0.2, min_lr 1e-8, threshold 5e-3), early stop after 512 epochs, <= 32768 epochs.
+// sigma eps, 0, 1); fit_hyper(kFitPol, DoublyRobust).
 __device__ int fit_dr(const RecView &V, const Chunk &K, TrainLds &S, Coop &C,
                       const FitNoise &F, const double *adam_tab, float *tr) {
+  constexpr FitHyper H = fit_hyper(kFitPol, AG_BIDDER_DOUBLY_ROBUST);
   const int tid = threadIdx.x;
   adam_reset(S);
-  double lr = 7e-3;
-  Plateau pl{INFINITY, 5e-3, 0.2, 1e-8, 0, 100};
-  Stopper sp{INFINITY, -1, 512};
+  double lr = H.lr;
+  Plateau pl = plateau_of(H);
+  Stopper sp = stopper_of(H);
   const double n = (double)K.n;
   int e = 0;
-  for (; e < kDrEpochs && e < F.epochs; ++e) {
+  for (; e < H.max_epochs && e < F.epochs; ++e) {
     int64_t acc[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) acc[j] = 0;
@@ -956,7 +880,7 @@ __device__ int fit_dr(const RecView &V, const Chunk &K, TrainLds &S, Coop &C,
     exact_totals<16>(acc, S, C);
     const float loss = (float)(fxv(S.tot[24], S.tot[25]) / n);
     const float g = tid < 12 ? (float)(fxv(S.tot[2 * tid], S.tot[2 * tid + 1]) / n) : 0.0f;
-    adam_step_block(S, S.pol, 12, g, e, lr, (float)1e-4, adam_tab);
+    adam_step_block(S, S.pol, 12, g, e, lr, H.wd, adam_tab);
     if (tid == 0 && tr) tr[e] = loss;
     plateau_step(pl, loss, lr);
     const bool stop = stop_step(sp, e, loss);
@@ -964,7 +888,7 @@ __device__ int fit_dr(const RecView &V, const Chunk &K, TrainLds &S, Coop &C,
     __syncthreads();
     if (stop || S.stop) return e + 1;
   }
-  if (e < kDrEpochs && tid == 0) S.exhausted = 1;
+  if (e < H.max_epochs && tid == 0) S.exhausted = 1;
   return e;
 }
 
@@ -1008,23 +932,22 @@ __device__ __forceinline__ void dm_rec(int64_t (&acc)[16], const float *pol, con
 }
 
 // ValueLearningBidder's policy fit (inference 'policy', src/Bidder.py:258-303): loss
-// -mean(W(ctr, value, g~) (V - V g~)), g~ = clip(mu + sigma eps, 0, 1); Adam(lr 2e-3, wd
-// 1e-6, AMSGrad), ReduceLROnPlateau(patience 100, factor 0.1, min_lr 1e-7), early stop after
-// 256 epochs, <= 16384 epochs. Exact fixed-point sums (bounded terms).
+// -mean(W(ctr, value, g~) (V - V g~)), g~ = clip(mu + sigma eps, 0, 1); fit_hyper(kFitPol,
+// ValueLearning). Exact fixed-point sums (bounded terms).
 __device__ int fit_dm(const RecView &V, const Chunk &K, TrainLds &S, Coop &C, const FitNoise &F,
                       const double *adam_tab, float *tr) {
+  constexpr FitHyper H = fit_hyper(kFitPol, AG_BIDDER_VALUE_LEARNING);
   const int tid = threadIdx.x;
   adam_reset(S);
-  double lr = 2e-3;
-  Plateau pl{INFINITY, 1e-4, 0.1, 1e-7, 0, 100};
-  Stopper sp{INFINITY, -1, 256};
+  double lr = H.lr;
+  Plateau pl = plateau_of(H);
+  Stopper sp = stopper_of(H);
   const double n = (double)K.n;
   int e = 0;
-  for (; e < kInitEpochs && e < F.epochs; ++e) {
+  for (; e < H.max_epochs && e < F.epochs; ++e) {
     int64_t acc[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) acc[j] = 0;
-    if (!(AG_DR_ABLATE_XCHG & 2))
     each_record(V, K.nb, [&](int64_t j, auto L) {
       constexpr bool l = decltype(L)::value;
       dm_rec(acc, S.pol, S.wr, V.template ctr_<l>(j), V.template val_<l>(j), fit_eps(F, e, K.c0 + j), S.tab);
@@ -1035,15 +958,33 @@ __device__ int fit_dm(const RecView &V, const Chunk &K, TrainLds &S, Coop &C, co
     exact_totals<16>(acc, S, C);
     const float loss = (float)(fxv(S.tot[24], S.tot[25]) / n);
     const float g = tid < 12 ? (float)(fxv(S.tot[2 * tid], S.tot[2 * tid + 1]) / n) : 0.0f;
-    adam_step_block(S, S.pol, 12, g, e, lr, (float)1e-6, adam_tab);
+    adam_step_block(S, S.pol, 12, g, e, lr, H.wd, adam_tab);
     if (tid == 0 && tr) tr[e] = loss;
     plateau_step(pl, loss, lr);
     const bool stop = stop_step(sp, e, loss);
     __syncthreads();
     if (stop) return e + 1;
   }
-  if (e < kInitEpochs && tid == 0) S.exhausted = 1;
+  if (e < H.max_epochs && tid == 0) S.exhausted = 1;
   return e;
+}
+
+// DoublyRobustBidder's estimated utilities (src/Bidder.py:541-546) of the workgroup's slice
+// [c0, c0 + nb) of the agent's records R, with the fitted win-rate model wr: written to eu
+// (global, the agent's) and, the slice's first `cap`, to the LDS row lfe of the record cache
+// (cap = 0: no cache). each_record's thread mapping: a thread reads back what it wrote.
+__device__ __forceinline__ void estimated_utilities(const DrRecords &R, int64_t c0, int64_t nb, const float *wr,
+                                                    double *eu, const uint64_t *tab, float *lfe = nullptr,
+                                                    int64_t cap = 0) {
+  for (int64_t j = threadIdx.x; j < nb; j += kDrThreads) {
+    const int64_t i = c0 + j;
+    const double c = (double)(float)R.ctr[i], v = (double)(float)R.value[i], g = (double)(float)R.gamma[i];
+    const double z = c * (double)wr[0] + v * (double)wr[1] + g * (double)wr[2] + (double)wr[3];
+    const float W = (float)(1.0 / (1.0 + agexp::exp(-z, tab)));
+    const double Vv = R.ctr[i] * R.value[i], P = R.ctr[i] * R.value[i] * R.gamma[i];
+    eu[i] = (double)W * (Vv - P);
+    if (j < cap) lfe[j] = (float)eu[i];
+  }
 }
 
 // per-record gradient of a policy loss term from d/dmu and d/dsigma (policy_bwd's order)
@@ -1188,11 +1129,9 @@ __global__ __launch_bounds__(kDrThreads, PH == 0 ? AG_DR_PH0_MIN_WAVES : AG_DR_P
   if (tid == 0) S.stop = S.exhausted = 0;
   __syncthreads();
   DrRecords R{R0.ctr + s0, R0.value + s0, R0.gamma + s0, R0.prop + s0, R0.util + s0, R0.won + s0};
-  const int64_t per = (n + nblk - 1) / nblk;
-  const int64_t c0 = (int64_t)rank * per < n ? (int64_t)rank * per : n;
-  const Chunk K{c0, (c0 + per < n ? c0 + per : n) - c0, n};
-  // the agent's exchange region [2][nblk][32] (its workgroups have consecutive block indices)
-  // the agent's exchange region: [2][nblk][32] parity buffers, then [nblk][32] accumulator rows
+  const Chunk K = wg_slice(n, nblk, rank);
+  // the agent's exchange region (its workgroups have consecutive block indices): [2][nblk][32]
+  // parity buffers, then [nblk][32] accumulator rows
   int64_t *preg = partials + (size_t)(blockIdx.x - rank) * 3 * 32;
   unsigned *abar = barriers + (size_t)bar_off[a] * kBarLineWords;
   Coop C{rank, nblk, preg, abar, 0, preg + (size_t)2 * nblk * 32, abar + (size_t)bar_lines(nblk) * kBarLineWords, 0u};
@@ -1219,11 +1158,13 @@ __global__ __launch_bounds__(kDrThreads, PH == 0 ? AG_DR_PH0_MIN_WAVES : AG_DR_P
     __syncthreads();
   }
   const RecView V{R, eu_ws + s0, K.c0, lf, lw, cap};
-  float *tr = (traces && lead) ? traces + (size_t)a * 3 * kDrEpochs : nullptr;
+  // the agent's trace rows from one pointer (tr, tr + kDrEpochs, tr + 2 kDrEpochs: trace_row's
+  // rows, kept as offsets -- a trace_row call per fit costs phase 1 four more spilled SGPRs)
+  float *tr = (traces && lead) ? trace_row(traces, a, kFitWr) : nullptr;
   if constexpr (PH == 0) {
     int ep0 = 0, stat = 0;
     if (bk == AG_BIDDER_DOUBLY_ROBUST) {
-      ep0 = fit_winrate(V, K, S, C, 256, 0.2, 1024, adam_tab, tr);
+      ep0 = fit_winrate(V, K, S, C, fit_hyper(kFitWr, AG_BIDDER_DOUBLY_ROBUST), adam_tab, tr);
     } else {  // ValueLearningBidder
       int64_t acc[1] = {0};
       each_record(V, K.nb, [&](int64_t j, auto L) { acc[0] += V.template won_<decltype(L)::value>(j) != 0.0 ? 1 : 0; });
@@ -1231,7 +1172,7 @@ __global__ __launch_bounds__(kDrThreads, PH == 0 ? AG_DR_PH0_MIN_WAVES : AG_DR_P
       if (S.tot[0] == 0 && S.tot[1] == 0)
         stat = 1;  // src/Bidder.py:206-211: revert to Gaussian shading, nothing trained
       else
-        ep0 = fit_winrate(V, K, S, C, 100, 0.1, 512, adam_tab, tr);
+        ep0 = fit_winrate(V, K, S, C, fit_hyper(kFitWr, AG_BIDDER_VALUE_LEARNING), adam_tab, tr);
     }
     if (!lead) return;
     if (tid == 0) {
@@ -1245,17 +1186,7 @@ __global__ __launch_bounds__(kDrThreads, PH == 0 ? AG_DR_PH0_MIN_WAVES : AG_DR_P
     int ep1 = 0, ep2 = 0;
     int stat = 0;
     if (bk == AG_BIDDER_DOUBLY_ROBUST) {
-      // estimated utilities of this workgroup's records with the fitted model (src/Bidder.py:541-546)
-      double *eu = eu_ws + s0;
-      for (int64_t j = tid; j < K.nb; j += kDrThreads) {
-        const int64_t i = K.c0 + j;
-        const double c = (double)(float)R.ctr[i], v = (double)(float)R.value[i], g = (double)(float)R.gamma[i];
-        const double z = c * (double)S.wr[0] + v * (double)S.wr[1] + g * (double)S.wr[2] + (double)S.wr[3];
-        const float W = (float)(1.0 / (1.0 + agexp::exp(-z, S.tab)));
-        const double Vv = R.ctr[i] * R.value[i], P = R.ctr[i] * R.value[i] * R.gamma[i];
-        eu[i] = (double)W * (Vv - P);
-        if (j < cap) lf[kFEu * cap + j] = (float)eu[i];
-      }
+      estimated_utilities(R, K.c0, K.nb, S.wr, eu_ws + s0, S.tab, lf + kFEu * cap, cap);
       __syncthreads();
       if (!initialised[a]) ep1 = fit_imitation(V, K, S, C, adam_tab, tr ? tr + kDrEpochs : nullptr);
       ep2 = fit_dr(V, K, S, C, F, adam_tab, tr ? tr + 2 * kDrEpochs : nullptr);
@@ -1302,7 +1233,6 @@ __global__ __launch_bounds__(kDrThreads, PH == 0 ? AG_DR_PH0_MIN_WAVES : AG_DR_P
 // A policy fit that runs out of host-drawn noise epochs (ag_bidder_rp_noise) waits, with its
 // state kept, for the next window: the drop-in update draws the reference's torch noise
 // window by window and never re-runs a fit.
-enum { kFitWins = 0, kFitWr, kFitEu, kFitInit, kFitPol, kFitDone };
 struct FitSt {
   int32_t fit, epoch, status, have_tot, need_noise, pad0;
   int32_t ep[3], pad1;
@@ -1314,30 +1244,15 @@ struct FitSt {
 };
 
 // the learner's state on entering `fit` (the persistent fits' initialisations)
-__device__ __forceinline__ void fit_enter(FitSt &st, int fit, int bk, int mode) {
+__device__ __forceinline__ void fit_enter(FitSt &st, int fit, int bk) {
   st.fit = fit;
   st.epoch = 0;
   for (int j = 0; j < 16; ++j) st.adam.ea[j] = st.adam.es[j] = st.adam.mx[j] = 0.0f;
-  const bool dr = bk == AG_BIDDER_DOUBLY_ROBUST;
-  if (fit == kFitWr) {
-    st.lr = 3e-3;
-    st.pl = dr ? Plateau{INFINITY, 1e-4, 0.2, 1e-7, 0, 256} : Plateau{INFINITY, 1e-4, 0.1, 1e-7, 0, 100};
-    st.sp = Stopper{INFINITY, -1, dr ? 1024 : 512};
-  } else if (fit == kFitInit) {
-    st.lr = 1e-3;
-    st.sp = Stopper{INFINITY, -1, 512};
-  } else if (fit == kFitPol) {
-    if (dr) {
-      st.lr = 7e-3;
-      st.pl = Plateau{INFINITY, 5e-3, 0.2, 1e-8, 0, 100};
-      st.sp = Stopper{INFINITY, -1, 512};
-    } else {
-      st.lr = 2e-3;
-      st.pl = Plateau{INFINITY, 1e-4, 0.1, 1e-7, 0, 100};
-      st.sp = Stopper{INFINITY, -1, 256};
-    }
-  }
-  (void)mode;
+  if (fit != kFitWr && fit != kFitInit && fit != kFitPol) return;
+  const FitHyper H = fit_hyper(fit, bk);
+  st.lr = H.lr;
+  if (fit != kFitInit) st.pl = plateau_of(H);  // (the imitation has no scheduler)
+  st.sp = stopper_of(H);
 }
 
 // the fit after `st.fit` ended (the reference's order, src/Bidder.py:229-325, :500-615)
@@ -1350,14 +1265,10 @@ __device__ __forceinline__ void fit_after(FitSt &st, int bk, int mode, int init)
     case kFitInit: nxt = kFitPol; break;
     default: nxt = kFitDone;
   }
-  fit_enter(st, nxt, bk, mode);
+  fit_enter(st, nxt, bk);
 }
 
-__device__ __forceinline__ int fit_max_epochs(int fit, int bk) {
-  if (fit == kFitWr) return kWrEpochs;
-  if (fit == kFitInit) return kInitEpochs;
-  return bk == AG_BIDDER_DOUBLY_ROBUST ? kDrEpochs : kInitEpochs;
-}
+__device__ __forceinline__ int fit_max_epochs(int fit, int bk) { return fit_hyper(fit, bk).max_epochs; }
 
 // step 1 (thread 0 with threads 0..15 for Adam): the learner's state after the epoch whose
 // summed partials are tot (hi, lo pairs); n: the learner's records over all ranks
@@ -1369,7 +1280,7 @@ __device__ __forceinline__ void fit_step(FitSt &st, const int64_t *tot, double n
     if (st.fit == kFitWins) {
       if (tot[0] == 0 && tot[1] == 0) {  // no wins: revert to Gaussian shading (src/Bidder.py:206-211)
         st.status = 1;
-        fit_enter(st, kFitDone, bk, mode);
+        fit_enter(st, kFitDone, bk);
       } else {
         fit_after(st, bk, mode, init);
       }
@@ -1390,8 +1301,7 @@ __device__ __forceinline__ void fit_step(FitSt &st, const int64_t *tot, double n
   if (np == 0) return;
   // Adam: thread j steps parameter j (adam_step_block's arithmetic)
   const int e = st.epoch;
-  const float wd = st.fit == kFitWr ? (float)1e-6 : (st.fit == kFitInit || bk == AG_BIDDER_DOUBLY_ROBUST ? (float)1e-4
-                                                                                                         : (float)1e-6);
+  const float wd = fit_hyper(st.fit, bk).wd;
   double bc1;
   float bc2f;
   if (bcp) {  // adam_tab[e], adam_tab[kDrEpochs + e] fetched by the caller
@@ -1417,10 +1327,10 @@ __device__ __forceinline__ void fit_step(FitSt &st, const int64_t *tot, double n
     const bool nan = loss != loss && st.fit == kFitPol && bk == AG_BIDDER_DOUBLY_ROBUST;
     st.epoch = e + 1;
     if (stop || nan || st.epoch >= fit_max_epochs(st.fit, bk)) {
-      st.ep[st.fit == kFitWr ? 0 : (st.fit == kFitInit ? 1 : 2)] = st.epoch;
+      st.ep[fit_slot(st.fit)] = st.epoch;
       if (nan) {
         st.status = -2;  // the reference exits (src/Bidder.py:592-600)
-        fit_enter(st, kFitDone, bk, mode);
+        fit_enter(st, kFitDone, bk);
       } else {
         fit_after(st, bk, mode, init);
       }
@@ -1429,10 +1339,65 @@ __device__ __forceinline__ void fit_step(FitSt &st, const int64_t *tot, double n
   __syncthreads();
 }
 
-// step 2: this workgroup's exact partial sums (S.tot, 2 NV words) of the learner's epoch
-template <int NV>
-__device__ __forceinline__ void rp_block(const int64_t (&acc)[NV], TrainLds &S) {
-  block_sums<NV>(acc, S.w, S.tot);
+// step 2: this workgroup's exact terms of the learner's current epoch (st.fit at st.epoch,
+// the models in st) over its nb records V -> S.tot; returns the words to sum (fit_words). PH:
+// the fits of phase 0 (win count, win-rate) or 1 (imitation, the DR / DM policy fit). i0: the
+// rsample index of local record 0 -- its global index over all ranks, so a rank holding a
+// shard keeps the draws of the one-process fit. A view with cap = 0 reads every record from
+// the store. (k_bidder_epoch and k_bidder_pipe; the persistent fits loop over the same terms.)
+template <int PH>
+__device__ __forceinline__ int epoch_partial(const FitSt &st, const RecView &V, int64_t nb, int bk, const FitNoise &F,
+                                             int64_t i0, TrainLds &S) {
+  const int tid = threadIdx.x;
+  const int64_t nrec = nb > tid ? (nb - tid + kDrThreads - 1) / kDrThreads : 0;
+  if constexpr (PH == 0) {
+    if (st.fit == kFitWins) {
+      int64_t acc[1] = {0};
+      each_record(V, nb, [&](int64_t j, auto L) { acc[0] += V.template won_<decltype(L)::value>(j) != 0.0 ? 1 : 0; });
+      block_sums<1>(acc, S.w, S.tot);
+      return fit_words(kFitWins);
+    }
+    int64_t acc[5] = {0, 0, 0, 0, 0};
+    const double w0 = (double)st.wr[0], w1 = (double)st.wr[1], w2 = (double)st.wr[2], w3 = (double)st.wr[3];
+    each_record(V, nb, [&](int64_t j, auto L) {
+      constexpr bool l = decltype(L)::value;
+      const double c = V.template ctr_<l>(j), v = V.template val_<l>(j);
+      wr_pair(acc, c, v, V.template gam_<l>(j), V.template won_<l>(j), w0, w1, w2, w3, S.tab);
+    });
+    wr_unbias(acc, nrec);
+    block_sums<5>(acc, S.w, S.tot);
+    return fit_words(kFitWr);
+  } else {
+    int64_t acc[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = 0;
+    const int e = st.epoch;
+    if (st.fit == kFitInit) {
+      each_record(V, nb, [&](int64_t j, auto L) {
+        constexpr bool l = decltype(L)::value;
+        imit_rec(acc, st.pol, V.template ctr_<l>(j), V.template val_<l>(j), V.template gam_<l>(j), S.tab);
+      });
+#pragma unroll
+      for (int q = 0; q < 14; ++q) fx_unbias(acc[q], nrec);
+    } else if (bk == AG_BIDDER_DOUBLY_ROBUST) {
+      each_record(V, nb, [&](int64_t j, auto L) {
+        constexpr bool l = decltype(L)::value;
+        dr_rec(acc, st.pol, st.wr, V.template ctr_<l>(j), V.template val_<l>(j), V.template gam_<l>(j),
+               V.template prop_<l>(j), V.template util_<l>(j) - V.template eut_<l>(j), fit_eps(F, e, i0 + j), S.tab);
+      });
+#pragma unroll
+      for (int q = 0; q < 13; ++q) fx_unbias(acc[q], nrec);
+    } else {
+      each_record(V, nb, [&](int64_t j, auto L) {
+        constexpr bool l = decltype(L)::value;
+        dm_rec(acc, st.pol, st.wr, V.template ctr_<l>(j), V.template val_<l>(j), fit_eps(F, e, i0 + j), S.tab);
+      });
+#pragma unroll
+      for (int q = 0; q < 13; ++q) fx_unbias(acc[q], nrec);
+    }
+    block_sums<16>(acc, S.w, S.tot);
+    return fit_words(kFitPol);
+  }
 }
 
 __global__ __launch_bounds__(kDrThreads) void k_bidder_epoch(
@@ -1456,28 +1421,17 @@ __global__ __launch_bounds__(kDrThreads) void k_bidder_epoch(
   __syncthreads();
   const double n = (double)n_total[a];
   if (st.fit != kFitDone && st.have_tot) {
-    float *tr = (traces && g_base[a] == 0 && rank == 0 && st.fit >= kFitWr)
-                    ? traces + ((size_t)a * 3 + (st.fit == kFitWr ? 0 : (st.fit == kFitInit ? 1 : 2))) * kDrEpochs
-                    : nullptr;
+    float *tr =
+        (traces && g_base[a] == 0 && rank == 0 && st.fit >= kFitWr) ? trace_row(traces, a, st.fit) : nullptr;
     fit_step(st, tot_in + (size_t)a * 32, n, bk, mode, init, adam_tab, s_grad, &s_loss, &s_np, tr);
   }
-  const int64_t s0 = offsets[a], nl = offsets[a + 1] - s0;
-  const int64_t per = (nl + nblk - 1) / nblk;
-  const int64_t c0 = (int64_t)rank * per < nl ? (int64_t)rank * per : nl;
-  const int64_t nb = (c0 + per < nl ? c0 + per : nl) - c0;
-  const DrRecords R{R0.ctr + s0 + c0, R0.value + s0 + c0, R0.gamma + s0 + c0, R0.prop + s0 + c0, R0.util + s0 + c0,
-                    R0.won + s0 + c0};
-  double *eu = eu_ws + s0 + c0;
+  const int64_t s0 = offsets[a];
+  const Chunk K = wg_slice(offsets[a + 1] - s0, nblk, rank);
+  // this workgroup's records (a slice of the agent's) as local records 0 .. nb - 1
+  const int64_t r0 = s0 + K.c0;
+  const DrRecords R{R0.ctr + r0, R0.value + r0, R0.gamma + r0, R0.prop + r0, R0.util + r0, R0.won + r0};
   if (st.fit == kFitEu) {
-    // estimated utilities of this workgroup's records with the fitted win-rate model
-    // (src/Bidder.py:541-546; k_bidder_train<1>'s arithmetic); the same thread reads them back
-    for (int64_t j = tid; j < nb; j += kDrThreads) {
-      const double c = (double)(float)R.ctr[j], v = (double)(float)R.value[j], g = (double)(float)R.gamma[j];
-      const double z = c * (double)st.wr[0] + v * (double)st.wr[1] + g * (double)st.wr[2] + (double)st.wr[3];
-      const float W = (float)(1.0 / (1.0 + agexp::exp(-z, S.tab)));
-      const double Vv = R.ctr[j] * R.value[j], P = R.ctr[j] * R.value[j] * R.gamma[j];
-      eu[j] = (double)W * (Vv - P);
-    }
+    estimated_utilities(R, 0, K.nb, st.wr, eu_ws + r0, S.tab);
     __syncthreads();
     if (tid == 0) fit_after(st, bk, mode, init);
     __syncthreads();
@@ -1490,47 +1444,10 @@ __global__ __launch_bounds__(kDrThreads) void k_bidder_epoch(
   if (active) {
     const FitNoise F{noise ? noise - (int64_t)noise_e0 * noise_n : nullptr, noise_n, noise_seed, (uint32_t)a,
                      1 << 30};
-    const int64_t gb = g_base[a] + c0;  // the global index of record 0 of this chunk (the noise's)
-    const int e = st.epoch;
-    const int64_t nrec = nb > tid ? (nb - tid + kDrThreads - 1) / kDrThreads : 0;
-    if (st.fit == kFitWins) {
-      int64_t acc[1] = {0};
-      for (int64_t j = tid; j < nb; j += kDrThreads) acc[0] += R.won[j] != 0 ? 1 : 0;
-      rp_block<1>(acc, S);
-    } else if (st.fit == kFitWr) {
-      int64_t acc[5] = {0, 0, 0, 0, 0};
-      const double w0 = (double)st.wr[0], w1 = (double)st.wr[1], w2 = (double)st.wr[2], w3 = (double)st.wr[3];
-      for (int64_t j = tid; j < nb; j += kDrThreads) {
-        const double c = (double)(float)R.ctr[j], v = (double)(float)R.value[j];
-        wr_row(acc, c, v, (double)(float)R.gamma[j], (double)R.won[j], false, w0, w1, w2, w3, S.tab);
-        wr_row(acc, c, v, 0.0, 0.0, true, w0, w1, w2, w3, S.tab);
-      }
-      wr_unbias(acc, nrec);
-      rp_block<5>(acc, S);
-    } else {
-      int64_t acc[16];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc[j] = 0;
-      if (st.fit == kFitInit) {
-        for (int64_t j = tid; j < nb; j += kDrThreads)
-          imit_rec(acc, st.pol, (double)(float)R.ctr[j], (double)(float)R.value[j], (double)(float)R.gamma[j], S.tab);
-#pragma unroll
-        for (int q = 0; q < 14; ++q) fx_unbias(acc[q], nrec);
-      } else if (bk == AG_BIDDER_DOUBLY_ROBUST) {
-        for (int64_t j = tid; j < nb; j += kDrThreads)
-          dr_rec(acc, st.pol, st.wr, (double)(float)R.ctr[j], (double)(float)R.value[j], (double)(float)R.gamma[j],
-                 (float)R.prop[j], (double)(float)R.util[j] - (double)(float)eu[j], fit_eps(F, e, gb + j), S.tab);
-#pragma unroll
-        for (int q = 0; q < 13; ++q) fx_unbias(acc[q], nrec);
-      } else {
-        for (int64_t j = tid; j < nb; j += kDrThreads)
-          dm_rec(acc, st.pol, st.wr, (double)(float)R.ctr[j], (double)(float)R.value[j], fit_eps(F, e, gb + j), S.tab);
-#pragma unroll
-        for (int q = 0; q < 13; ++q) fx_unbias(acc[q], nrec);
-      }
-      rp_block<16>(acc, S);
-    }
-    const int W = st.fit == kFitWins ? 2 : (st.fit == kFitWr ? 10 : 32);
+    const RecView V{R, eu_ws + r0, 0, nullptr, nullptr, 0};  // no record cache: every field from the store
+    const int64_t i0 = g_base[a] + K.c0;  // the global index, over all ranks, of this slice's record 0
+    const int W = st.fit == kFitWins || st.fit == kFitWr ? epoch_partial<0>(st, V, K.nb, bk, F, i0, S)
+                                                         : epoch_partial<1>(st, V, K.nb, bk, F, i0, S);
     // the agent's region: accumulator rows [bar_lines(nblk)][32], barrier lines
     agcoop::agent_reduce_nowait(bars + (size_t)bar_off[a] * agcoop::kBarLineWords,
                                 acc_rows + (size_t)bar_off[a] * 32, 32, rank, nblk, S.tot, W,
@@ -1585,73 +1502,9 @@ struct PipeArgs {
   long long *prof;              // diagnostics (AG_PIPE_PROF): [G][8] wall-clock ticks per part, or NULL
 };
 
-// this workgroup's slice [c0, c0 + nb) of n records over G workgroups
-__device__ __forceinline__ void pipe_chunk(int64_t n, int G, int rank, int64_t &c0, int64_t &nb) {
-  const int64_t per = (n + G - 1) / G;
-  c0 = (int64_t)rank * per < n ? (int64_t)rank * per : n;
-  nb = (c0 + per < n ? c0 + per : n) - c0;
-}
-
 template <int PH>
 __device__ __forceinline__ bool pipe_in_phase(int fit) {
   return PH == 0 ? (fit == kFitWins || fit == kFitWr) : (fit == kFitEu || fit == kFitInit || fit == kFitPol);
-}
-
-// this workgroup's exact partial sums of the learner's current epoch -> S.tot; returns the
-// words to sum (k_bidder_epoch's step 2)
-template <int PH>
-__device__ __forceinline__ int pipe_partial(const FitSt &st, const RecView &V, int64_t nb, int bk, const FitNoise &F,
-                                            TrainLds &S) {
-  const int tid = threadIdx.x;
-  const int64_t nrec = nb > tid ? (nb - tid + kDrThreads - 1) / kDrThreads : 0;
-  if constexpr (PH == 0) {
-    if (st.fit == kFitWins) {
-      int64_t acc[1] = {0};
-      each_record(V, nb, [&](int64_t j, auto L) { acc[0] += V.template won_<decltype(L)::value>(j) != 0.0 ? 1 : 0; });
-      block_sums<1>(acc, S.w, S.tot);
-      return 2;
-    }
-    int64_t acc[5] = {0, 0, 0, 0, 0};
-    const double w0 = (double)st.wr[0], w1 = (double)st.wr[1], w2 = (double)st.wr[2], w3 = (double)st.wr[3];
-    each_record(V, nb, [&](int64_t j, auto L) {
-      constexpr bool l = decltype(L)::value;
-      const double c = V.template ctr_<l>(j), v = V.template val_<l>(j);
-      wr_pair(acc, c, v, V.template gam_<l>(j), V.template won_<l>(j), w0, w1, w2, w3, S.tab);
-    });
-    wr_unbias(acc, nrec);
-    block_sums<5>(acc, S.w, S.tot);
-    return 10;
-  } else {
-    int64_t acc[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = 0;
-    const int e = st.epoch;
-    if (st.fit == kFitInit) {
-      each_record(V, nb, [&](int64_t j, auto L) {
-        constexpr bool l = decltype(L)::value;
-        imit_rec(acc, st.pol, V.template ctr_<l>(j), V.template val_<l>(j), V.template gam_<l>(j), S.tab);
-      });
-#pragma unroll
-      for (int q = 0; q < 14; ++q) fx_unbias(acc[q], nrec);
-    } else if (bk == AG_BIDDER_DOUBLY_ROBUST) {
-      each_record(V, nb, [&](int64_t j, auto L) {
-        constexpr bool l = decltype(L)::value;
-        dr_rec(acc, st.pol, st.wr, V.template ctr_<l>(j), V.template val_<l>(j), V.template gam_<l>(j),
-               V.template prop_<l>(j), V.template util_<l>(j) - V.template eut_<l>(j), fit_eps(F, e, V.c0 + j), S.tab);
-      });
-#pragma unroll
-      for (int q = 0; q < 13; ++q) fx_unbias(acc[q], nrec);
-    } else {
-      each_record(V, nb, [&](int64_t j, auto L) {
-        constexpr bool l = decltype(L)::value;
-        dm_rec(acc, st.pol, st.wr, V.template ctr_<l>(j), V.template val_<l>(j), fit_eps(F, e, V.c0 + j), S.tab);
-      });
-#pragma unroll
-      for (int q = 0; q < 13; ++q) fx_unbias(acc[q], nrec);
-    }
-    block_sums<16>(acc, S.w, S.tot);
-    return 32;
-  }
 }
 
 // a slot's constants, read once into LDS (the rounds read nothing from global memory but the
@@ -1686,7 +1539,9 @@ __global__ __launch_bounds__(kDrThreads, PH == 0 ? 4 : AG_DR_PH1_MIN_WAVES) void
     P.init = A.initialised[a];
     P.n = (double)A.n_total[a];
     P.s0 = A.offsets[a];
-    pipe_chunk(A.offsets[a + 1] - P.s0, G, rank, P.c0, P.nb);
+    const Chunk K = wg_slice(A.offsets[a + 1] - P.s0, G, rank);
+    P.c0 = K.c0;
+    P.nb = K.nb;
     P.cap = A.lds_cap[i];
     P.off = (uint32_t)A.lds_off[i];
     P.nf = PH == 0 ? 3 : (bk == AG_BIDDER_DOUBLY_ROBUST ? 6 : 2);
@@ -1724,8 +1579,7 @@ __global__ __launch_bounds__(kDrThreads, PH == 0 ? 4 : AG_DR_PH1_MIN_WAVES) void
     return RecView{R, A.eu_ws + s0, P.c0, lf, reinterpret_cast<const uint8_t *>(lf + (size_t)P.nf * P.cap), P.cap};
   };
   auto tr_of = [&](int a, const FitSt &st) -> float * {
-    if (!A.traces || rank != 0 || st.fit < kFitWr) return nullptr;
-    return A.traces + ((size_t)a * 3 + (st.fit == kFitWr ? 0 : (st.fit == kFitInit ? 1 : 2))) * kDrEpochs;
+    return (A.traces && rank == 0 && st.fit >= kFitWr) ? trace_row(A.traces, a, st.fit) : nullptr;
   };
   auto step = [&](int i, const int64_t *tot, bool prefetched) {
     const PipeSlot &P = s_slot[i];
@@ -1741,19 +1595,8 @@ __global__ __launch_bounds__(kDrThreads, PH == 0 ? 4 : AG_DR_PH1_MIN_WAVES) void
     const int64_t nb = P.nb;
     const RecView V = view(P);
     if (PH == 1 && st.fit == kFitEu) {
-      // src/Bidder.py:541-546 with the fitted win-rate model (k_bidder_epoch's arithmetic);
-      // each_record's thread mapping, so a thread reads back what it wrote
-      double *eu = A.eu_ws + P.s0;
       float *lfe = reinterpret_cast<float *>(s_dyn + P.off) + (size_t)kFEu * V.cap;
-      for (int64_t j = tid; j < nb; j += kDrThreads) {
-        const int64_t r = V.c0 + j;
-        const double c = (double)(float)V.R.ctr[r], v = (double)(float)V.R.value[r], g = (double)(float)V.R.gamma[r];
-        const double z = c * (double)st.wr[0] + v * (double)st.wr[1] + g * (double)st.wr[2] + (double)st.wr[3];
-        const float W = (float)(1.0 / (1.0 + agexp::exp(-z, S.tab)));
-        const double Vv = V.R.ctr[r] * V.R.value[r], Pp = V.R.ctr[r] * V.R.value[r] * V.R.gamma[r];
-        eu[r] = (double)W * (Vv - Pp);
-        if (j < V.cap) lfe[j] = (float)eu[r];
-      }
+      estimated_utilities(V.R, V.c0, nb, st.wr, A.eu_ws + P.s0, S.tab, lfe, V.cap);
       __syncthreads();
       if (tid == 0) fit_after(st, bk, P.mode, P.init);
       __syncthreads();
@@ -1777,7 +1620,7 @@ __global__ __launch_bounds__(kDrThreads, PH == 0 ? 4 : AG_DR_PH1_MIN_WAVES) void
     const FitNoise F{A.noise ? A.noise + (A.noise_off ? A.noise_off[a] : 0) - (int64_t)A.noise_e0 * stride : nullptr,
                      stride, A.noise_seed, (uint32_t)a, 1 << 30};
     long long tp = A.prof && tid == 0 ? wall_clock64() : 0;
-    const int W = pipe_partial<PH>(st, V, nb, bk, F, S);
+    const int W = epoch_partial<PH>(st, V, nb, bk, F, V.c0, S);
     if (tid == 0) {
       s_bc[i][0] = b1;
       s_bc[i][1] = b2;
@@ -1808,7 +1651,7 @@ __global__ __launch_bounds__(kDrThreads, PH == 0 ? 4 : AG_DR_PH1_MIN_WAVES) void
   while (pend) {
     for (int i = 0; i < NA; ++i) {
       if (!(pend >> i & 1)) continue;
-      const int W = fst[i].fit == kFitWins ? 2 : (fst[i].fit == kFitWr ? 10 : 32);
+      const int W = fit_words(fst[i].fit);
       long long tf = A.prof && tid == 0 ? wall_clock64() : 0;
       agcoop::agent_allreduce_finish(A.bars + (size_t)i * A.lines * kBarLineWords, A.acc + (size_t)i * A.lines * 32, G,
                                      roots >> i & 1, &s_gen[i], W, S.tot);
@@ -1854,10 +1697,7 @@ __global__ void k_rp_init(int N, const int32_t *__restrict__ bkind, const int32_
   for (int j = 0; j < 4; ++j) f.wr[j] = state[(size_t)a * 16 + j];
   for (int j = 0; j < 12; ++j) f.pol[j] = state[(size_t)a * 16 + 4 + j];
   const int bk = bkind[a];
-  if (mask[a])
-    fit_enter(f, bk == AG_BIDDER_DOUBLY_ROBUST ? kFitWr : kFitWins, bk, bmode[a]);
-  else
-    fit_enter(f, kFitDone, bk, bmode[a]);
+  fit_enter(f, !mask[a] ? kFitDone : (bk == AG_BIDDER_DOUBLY_ROBUST ? kFitWr : kFitWins), bk);
   st[a] = f;
   if (parities == 2) st[N + a] = f;  // [2][N] states: parity 1 too -- the epoch launches never
                                      // write unmasked agents' rows
@@ -2174,6 +2014,155 @@ static int sort_records(ag_ctx *c, const ag_shading_samples *s, std::vector<int6
   return AG_OK;
 }
 
+// The block tables of a launch, from the workgroups per agent (nblk; 0: the agent is not in the
+// launch): workgroup b works on agent blk_agent[b] as its workgroup blk_rank[b] (an agent's
+// workgroups have consecutive indices); agent a's barrier lines (and accumulator rows) start
+// at line bar_off[a], lines_of(nblk[a]) of them, `lines` in all.
+struct BlockTables {
+  std::vector<int32_t> nblk, blk_agent, blk_rank, bar_off;
+  int lines = 0;
+};
+static void block_tables(BlockTables &T, int (*lines_of)(int nblk)) {
+  const int N = (int)T.nblk.size();
+  T.bar_off.assign(N, 0);
+  T.blk_agent.clear();
+  T.blk_rank.clear();
+  T.lines = 0;
+  for (int a = 0; a < N; ++a) {
+    if (!T.nblk[a]) continue;
+    T.bar_off[a] = T.lines;
+    T.lines += lines_of(T.nblk[a]);
+    for (int r = 0; r < T.nblk[a]; ++r) {
+      T.blk_agent.push_back(a);
+      T.blk_rank.push_back(r);
+    }
+  }
+}
+
+// One phase's launch of k_bidder_train (ag_bidder_update) for the learners `trained`: the
+// workgroups per learner and the record cache. Workgroups per learning bidder, co-resident (cooperative launch) when an agent has
+// several; capped to the resident grid (occupancy with the phase's largest record cache).
+// With AG_OPT_BIDDER_BLOCK_SAMPLES set: one per that many records. By default the
+// exact-sum learners (ValueLearning, DoublyRobust: results independent of the split)
+// share the resident grid in proportion to their records, >= kMinChunk records per
+// workgroup; a PolicyLearningBidder (fixed-order float sums: its result follows the split)
+// keeps one workgroup per kBidderChunk records. Both phases use the same rule with their
+// own grid.
+struct TrainPlan {
+  const void *fn = nullptr;
+  BlockTables T;
+  int G = 0, nf = 0;
+  bool multi = false;
+  int64_t rcap = 0;
+  size_t dyn = 0;
+};
+static int train_plan(ag_ctx *c, int ph, const std::vector<int64_t> &cnt, const std::vector<char> &trained,
+                      TrainPlan &P) {
+  ag_dr_ws &w = c->dr;
+  const int N = c->shape.num_agents;
+  P.fn = ph == 0 ? (const void *)k_bidder_train<0> : (const void *)k_bidder_train<1>;
+  const size_t lds_budget = ph == 0 ? kRecLdsBytes0 : kRecLdsBytes;
+  int &coop_blocks = ph == 0 ? w.coop_blocks0 : w.coop_blocks;
+  if (!coop_blocks) {
+    int per_cu = 0, cus = 0;
+    AG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, P.fn, kDrThreads, lds_budget));
+    AG_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    coop_blocks = per_cu * cus > 0 ? per_cu * cus : 1;
+  }
+  std::vector<int32_t> &nblk = P.T.nblk;
+  nblk.assign(N, 0);
+  int64_t want = 0, exact_recs = 0, fixed_blocks = 0;
+  int nf = 0;  // float fields of the record cache: 3 (win-rate, ValueLearning), 5 (PolicyLearning), 6 (DR)
+  for (int a = 0; a < N; ++a) {
+    const int bk = c->h_bkind[a];
+    if (!trained[a] || (ph == 0 && bk == AG_BIDDER_POLICY_LEARNING)) continue;
+    nf = std::max(nf, ph == 0 ? 3 : (bk == AG_BIDDER_DOUBLY_ROBUST ? 6 : (bk == AG_BIDDER_POLICY_LEARNING ? 5 : 3)));
+    if (c->bidder_chunk > 0 || bk == AG_BIDDER_POLICY_LEARNING) {
+      const int64_t chunk = c->bidder_chunk > 0 ? c->bidder_chunk : kBidderChunk;
+      nblk[a] = cnt[a] > 0 ? (int32_t)((cnt[a] + chunk - 1) / chunk) : 1;
+      fixed_blocks += nblk[a];
+    } else {
+      exact_recs += cnt[a];
+      nblk[a] = -1;
+    }
+  }
+  for (int a = 0; a < N; ++a) {
+    if (nblk[a] < 0) {
+      const int64_t avail = std::max<int64_t>(1, coop_blocks - fixed_blocks);
+      const int64_t share = exact_recs > 0 ? (int64_t)((double)avail * (double)cnt[a] / (double)exact_recs) : 1;
+      nblk[a] = (int32_t)std::max<int64_t>(1, std::min<int64_t>((cnt[a] + kMinChunk - 1) / kMinChunk, share));
+    }
+    want += nblk[a];
+  }
+  if (want > coop_blocks) {  // share the resident grid out
+    const double f = (double)coop_blocks / (double)want;
+    for (int a = 0; a < N; ++a)
+      if (nblk[a] > 1) nblk[a] = (int32_t)(nblk[a] * f) > 1 ? (int32_t)(nblk[a] * f) : 1;
+  }
+  // (an agent's lines: the tree's, then the grouped sums')
+  block_tables(P.T, [](int nb) { return bar_lines(nb) + agcoop::group_lines(nb); });
+  int64_t most = 0;  // records of the largest workgroup chunk
+  for (int a = 0; a < N; ++a) {
+    P.multi |= nblk[a] > 1;
+    if (nblk[a]) most = std::max<int64_t>(most, (cnt[a] + nblk[a] - 1) / nblk[a]);
+  }
+  P.G = (int)P.T.blk_agent.size();
+  if (P.multi && P.G > coop_blocks)
+    return ag_set_error(AG_ERR_UNSUPPORTED, "ag_bidder_update: %d learning bidders need more co-resident "
+                        "workgroups (%d) than the device holds (%d)", N, P.G, coop_blocks);
+  // record cache: [nf][cap] floats + [cap] bytes, cap a multiple of the block size
+  const int64_t rcap_fit = nf ? (int64_t)lds_budget / (4 * nf + 1) / kDrThreads * kDrThreads : 0;
+  P.rcap = std::min<int64_t>(rcap_fit, (most + kDrThreads - 1) / kDrThreads * kDrThreads);
+  if (c->bidder_cache >= 0) P.rcap = std::min<int64_t>(P.rcap, c->bidder_cache / kDrThreads * kDrThreads);
+  P.nf = nf;
+  P.dyn = ((size_t)P.rcap * (4 * nf + 1) + 15) / 16 * 16;
+  return AG_OK;
+}
+
+// ag_bidder_update's device tables (one buffer, shared by its two launches) and outputs
+struct TrainDev {
+  int64_t *part;
+  unsigned *bar;
+  int32_t *bagent, *brank, *nblk, *baroff;
+  float *wr;
+  int64_t *noff;
+  int32_t *epochs, *stat;
+};
+static int train_launch(ag_ctx *c, const TrainPlan &P, const TrainDev &D, const SortedRecs &SR, const float *noise,
+                        int32_t noise_epochs, float *traces, hipStream_t st) {
+  if (P.G == 0) return AG_OK;
+  ag_dr_ws &w = c->dr;
+  const int N = c->shape.num_agents;
+  AG_HIP(hipMemcpyAsync(D.bagent, P.T.blk_agent.data(), sizeof(int32_t) * P.G, hipMemcpyHostToDevice, st));
+  AG_HIP(hipMemcpyAsync(D.brank, P.T.blk_rank.data(), sizeof(int32_t) * P.G, hipMemcpyHostToDevice, st));
+  AG_HIP(hipMemcpyAsync(D.nblk, P.T.nblk.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
+  AG_HIP(hipMemcpyAsync(D.baroff, P.T.bar_off.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
+  if (P.T.lines) AG_HIP(hipMemsetAsync(D.bar, 0, sizeof(unsigned) * kBarLineWords * P.T.lines, st));
+  if (P.multi) AG_HIP(hipMemsetAsync(D.part, 0, sizeof(int64_t) * 96 * (size_t)P.G, st));  // accumulators
+  DrRecords R{SR.ctr, SR.val, SR.gam, SR.prop, SR.util, SR.won};
+  const int32_t *cbk = c->d_bkind, *cmode = w.mode, *cinit = w.init, *cbo = D.baroff;
+  const int32_t *cbagent = D.bagent, *cbrank = D.brank, *cnblk = D.nblk;
+  const int64_t *coff = SR.d_off, *cnoff = D.noff;
+  double *ceu = SR.eu;
+  float *cstate = w.state, *ctr = traces, *cwr = D.wr;
+  int32_t *cep = D.epochs, *cstat = D.stat;
+  int64_t *cpart = D.part;
+  unsigned *cbar = D.bar;
+  int cne = noise_epochs;
+  uint64_t cseed = c->fit_noise_seed;
+  const double *ctab = w.adam_tab;
+  int cnf = P.nf;
+  int64_t ccap = P.rcap;
+  void *args[] = {&cbk,    &cmode, &cbagent, &cbrank, &cnblk, &coff, &R,     &ceu,
+                  &cstate, &cwr,   &cinit,   &noise,  &cnoff, &cne,  &cseed, &ctab,
+                  &cep,    &cstat, &ctr,     &cpart,  &cbar,  &cbo,  &cnf,   &ccap};
+  if (P.multi)  // workgroups of one agent wait for each other: they must all be resident
+    AG_HIP(hipLaunchCooperativeKernel(P.fn, dim3(P.G), dim3(kDrThreads), args, P.dyn, st));
+  else
+    AG_HIP(hipLaunchKernel(P.fn, dim3(P.G), dim3(kDrThreads), args, P.dyn, st));
+  return AG_OK;
+}
+
 extern "C" {
 
 int ag_set_dr_state(ag_ctx *c, const float *state, const int32_t *initialised) {
@@ -2240,22 +2229,11 @@ int ag_bidder_update(ag_ctx *c, const ag_shading_samples *s, const int32_t *agen
   SortedRecs SR;
   if (int rc = sort_records(c, s, cnt, off, SR, st)) return rc;
   ag_dr_ws &w = c->dr;
-  const int64_t *d_off = SR.d_off;
-  double *b_ctr = SR.ctr, *b_val = SR.val, *b_gam = SR.gam, *b_prop = SR.prop, *b_util = SR.util, *b_eu = SR.eu;
-  uint8_t *b_won = SR.won;
   int64_t *d_noff = w.scratch;                       // [N] noise offsets
   int32_t *d_epochs = (int32_t *)(w.scratch + N);     // [N][3] epochs, then [N] status
   int32_t *d_stat = d_epochs + 3 * (size_t)N;
   AG_HIP(hipMemcpyAsync(d_noff, noise_offsets, sizeof(int64_t) * N, hipMemcpyHostToDevice, st));
   AG_HIP(hipMemsetAsync(d_epochs, 0, sizeof(int32_t) * 4 * N, st));
-  // Workgroups per learning bidder, co-resident (cooperative launch) when an agent has
-  // several; capped to the resident grid (occupancy with the phase's largest record cache).
-  // With AG_OPT_BIDDER_BLOCK_SAMPLES set: one per that many records. By default the
-  // exact-sum learners (ValueLearning, DoublyRobust: results independent of the split)
-  // share the resident grid in proportion to their records, >= kMinChunk records per
-  // workgroup; a PolicyLearningBidder (fixed-order float sums: its result follows the split)
-  // keeps one workgroup per kBidderChunk records. Both phases use the same rule with their
-  // own grid.
   // k_bidder_train, one group of workgroups per learner, by default: measured on the bench's
   // populations (profiles/r04j_*), the pipelined launches (k_bidder_pipe, every learner in
   // every workgroup) lose -- each round pays one epoch's serial step and tree climb per
@@ -2275,90 +2253,19 @@ int ag_bidder_update(ag_ctx *c, const ag_shading_samples *s, const int32_t *agen
     if ((int)pipe_slots.size() > kPipeMaxAgents) pipe_slots.clear();
     for (int a : pipe_slots) pipe_mask[a] = 1;
   }
-  auto is_learner = [&](int a) {
+  std::vector<char> trained(N, 0);  // k_bidder_train's learners: every learner in `agents` the pipe does not take
+  for (int a = 0; a < N; ++a) {
     const int bk = c->h_bkind[a];
-    return (bk == AG_BIDDER_VALUE_LEARNING || bk == AG_BIDDER_POLICY_LEARNING || bk == AG_BIDDER_DOUBLY_ROBUST) &&
-           !(agents && !agents[a]) && !pipe_mask[a];
-  };
-  struct Plan {
-    const void *fn = nullptr;
-    std::vector<int32_t> nblk, blk_agent, blk_rank, bar_off;
-    int G = 0, lines = 0, nf = 0;
-    bool multi = false;
-    int64_t rcap = 0;
-    size_t dyn = 0;
-  };
-  auto plan = [&](int ph, Plan &P) -> int {
-    P.fn = ph == 0 ? (const void *)k_bidder_train<0> : (const void *)k_bidder_train<1>;
-    const size_t lds_budget = ph == 0 ? kRecLdsBytes0 : kRecLdsBytes;
-    int &coop_blocks = ph == 0 ? w.coop_blocks0 : w.coop_blocks;
-    if (!coop_blocks) {
-      int per_cu = 0, cus = 0;
-      AG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, P.fn, kDrThreads, lds_budget));
-      AG_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-      coop_blocks = per_cu * cus > 0 ? per_cu * cus : 1;
-    }
-    std::vector<int32_t> &nblk = P.nblk;
-    nblk.assign(N, 0);
-    int64_t want = 0, exact_recs = 0, fixed_blocks = 0;
-    int nf = 0;  // float fields of the record cache: 3 (win-rate, ValueLearning), 5 (PolicyLearning), 6 (DR)
-    for (int a = 0; a < N; ++a) {
-      const int bk = c->h_bkind[a];
-      if (!is_learner(a) || (ph == 0 && bk == AG_BIDDER_POLICY_LEARNING)) continue;
-      nf = std::max(nf, ph == 0 ? 3 : (bk == AG_BIDDER_DOUBLY_ROBUST ? 6 : (bk == AG_BIDDER_POLICY_LEARNING ? 5 : 3)));
-      if (c->bidder_chunk > 0 || bk == AG_BIDDER_POLICY_LEARNING) {
-        const int64_t chunk = c->bidder_chunk > 0 ? c->bidder_chunk : kBidderChunk;
-        nblk[a] = cnt[a] > 0 ? (int32_t)((cnt[a] + chunk - 1) / chunk) : 1;
-        fixed_blocks += nblk[a];
-      } else {
-        exact_recs += cnt[a];
-        nblk[a] = -1;
-      }
-    }
-    for (int a = 0; a < N; ++a) {
-      if (nblk[a] < 0) {
-        const int64_t avail = std::max<int64_t>(1, coop_blocks - fixed_blocks);
-        const int64_t share = exact_recs > 0 ? (int64_t)((double)avail * (double)cnt[a] / (double)exact_recs) : 1;
-        nblk[a] = (int32_t)std::max<int64_t>(1, std::min<int64_t>((cnt[a] + kMinChunk - 1) / kMinChunk, share));
-      }
-      want += nblk[a];
-    }
-    if (want > coop_blocks) {  // share the resident grid out
-      const double f = (double)coop_blocks / (double)want;
-      for (int a = 0; a < N; ++a)
-        if (nblk[a] > 1) nblk[a] = (int32_t)(nblk[a] * f) > 1 ? (int32_t)(nblk[a] * f) : 1;
-    }
-    int64_t most = 0;  // records of the largest workgroup chunk
-    P.bar_off.assign(N, 0);
-    for (int a = 0; a < N; ++a) {
-      P.multi |= nblk[a] > 1;
-      if (nblk[a]) most = std::max<int64_t>(most, (cnt[a] + nblk[a] - 1) / nblk[a]);
-      P.bar_off[a] = P.lines;
-      P.lines += bar_lines(nblk[a]) + agcoop::group_lines(nblk[a]);  // (the tree's, then the grouped sums')
-      for (int r = 0; r < nblk[a]; ++r) {
-        P.blk_agent.push_back(a);
-        P.blk_rank.push_back(r);
-      }
-    }
-    P.G = (int)P.blk_agent.size();
-    if (P.multi && P.G > coop_blocks)
-      return ag_set_error(AG_ERR_UNSUPPORTED, "ag_bidder_update: %d learning bidders need more co-resident "
-                          "workgroups (%d) than the device holds (%d)", N, P.G, coop_blocks);
-    // record cache: [nf][cap] floats + [cap] bytes, cap a multiple of the block size
-    const int64_t rcap_fit = nf ? (int64_t)lds_budget / (4 * nf + 1) / kDrThreads * kDrThreads : 0;
-    P.rcap = std::min<int64_t>(rcap_fit, (most + kDrThreads - 1) / kDrThreads * kDrThreads);
-    if (c->bidder_cache >= 0) P.rcap = std::min<int64_t>(P.rcap, c->bidder_cache / kDrThreads * kDrThreads);
-    P.nf = nf;
-    P.dyn = ((size_t)P.rcap * (4 * nf + 1) + 15) / 16 * 16;
-    return AG_OK;
-  };
-  Plan P0, P1;
-  if (int rc = plan(0, P0)) return rc;
-  if (int rc = plan(1, P1)) return rc;
+    trained[a] = (bk == AG_BIDDER_VALUE_LEARNING || bk == AG_BIDDER_POLICY_LEARNING || bk == AG_BIDDER_DOUBLY_ROBUST) &&
+                 !(agents && !agents[a]) && !pipe_mask[a];
+  }
+  TrainPlan P0, P1;
+  if (int rc = train_plan(c, 0, cnt, trained, P0)) return rc;
+  if (int rc = train_plan(c, 1, cnt, trained, P1)) return rc;
   // device tables (shared by the two launches, rewritten in stream order): exchange
   // partials [G][2][32] i64; barrier lines [lines][32] u32; blk_agent [G], blk_rank [G],
   // agent_nblk [N], bar_off [N] i32; win-rate models [N][4] f32 (phase 0 -> phase 1)
-  const size_t gmax = (size_t)std::max(P0.G, P1.G), lmax = (size_t)std::max(P0.lines, P1.lines);
+  const size_t gmax = (size_t)std::max(P0.G, P1.G), lmax = (size_t)std::max(P0.T.lines, P1.T.lines);
   const size_t need_coop = sizeof(int64_t) * 96 * gmax + sizeof(unsigned) * kBarLineWords * lmax +
                            sizeof(int32_t) * (2 * gmax + 2 * (size_t)N) + sizeof(float) * 4 * N + 64;
   if (need_coop > w.coop_bytes) {
@@ -2368,40 +2275,17 @@ int ag_bidder_update(ag_ctx *c, const ag_shading_samples *s, const int32_t *agen
     AG_HIP(hipMalloc(&w.coop, need_coop));
     w.coop_bytes = need_coop;
   }
-  int64_t *d_part = (int64_t *)w.coop;
-  unsigned *d_bar = (unsigned *)(d_part + 96 * gmax);
-  int32_t *d_bagent = (int32_t *)(d_bar + kBarLineWords * lmax);
-  int32_t *d_brank = d_bagent + gmax;
-  int32_t *d_nblk = d_brank + gmax;
-  int32_t *d_baroff = d_nblk + N;
-  float *d_wr = (float *)(d_baroff + N);
-  auto launch = [&](const Plan &P) -> int {
-    if (P.G == 0) return AG_OK;
-    AG_HIP(hipMemcpyAsync(d_bagent, P.blk_agent.data(), sizeof(int32_t) * P.G, hipMemcpyHostToDevice, st));
-    AG_HIP(hipMemcpyAsync(d_brank, P.blk_rank.data(), sizeof(int32_t) * P.G, hipMemcpyHostToDevice, st));
-    AG_HIP(hipMemcpyAsync(d_nblk, P.nblk.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
-    AG_HIP(hipMemcpyAsync(d_baroff, P.bar_off.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
-    if (P.lines) AG_HIP(hipMemsetAsync(d_bar, 0, sizeof(unsigned) * kBarLineWords * P.lines, st));
-    if (P.multi) AG_HIP(hipMemsetAsync(d_part, 0, sizeof(int64_t) * 96 * (size_t)P.G, st));  // accumulators
-    DrRecords R{b_ctr, b_val, b_gam, b_prop, b_util, b_won};
-    const int32_t *cbk = c->d_bkind, *cmode = w.mode, *cinit = w.init, *cbo = d_baroff;
-    const int64_t *coff = d_off, *cnoff = d_noff;
-    double *ceu = b_eu;
-    float *cstate = w.state, *ctr = traces, *cwr = d_wr;
-    int cne = noise_epochs;
-    uint64_t cseed = c->fit_noise_seed;
-    const double *ctab = w.adam_tab;
-    int cnf = P.nf;
-    int64_t ccap = P.rcap;
-    void *args[] = {&cbk,  &cmode,  &d_bagent, &d_brank, &d_nblk, &coff,  &R,        &ceu,
-                    &cstate, &cwr,  &cinit,    &noise,   &cnoff,  &cne,   &cseed,    &ctab,
-                    &d_epochs, &d_stat, &ctr,  &d_part,  &d_bar,  &cbo,   &cnf,      &ccap};
-    if (P.multi)  // workgroups of one agent wait for each other: they must all be resident
-      AG_HIP(hipLaunchCooperativeKernel(P.fn, dim3(P.G), dim3(kDrThreads), args, P.dyn, st));
-    else
-      AG_HIP(hipLaunchKernel(P.fn, dim3(P.G), dim3(kDrThreads), args, P.dyn, st));
-    return AG_OK;
-  };
+  TrainDev D;
+  D.part = (int64_t *)w.coop;
+  D.bar = (unsigned *)(D.part + 96 * gmax);
+  D.bagent = (int32_t *)(D.bar + kBarLineWords * lmax);
+  D.brank = D.bagent + gmax;
+  D.nblk = D.brank + gmax;
+  D.baroff = D.nblk + N;
+  D.wr = (float *)(D.baroff + N);
+  D.noff = d_noff;
+  D.epochs = d_epochs;
+  D.stat = d_stat;
   FitSt *pst = nullptr;
   if (!pipe_slots.empty()) {
     pst = pipe_fitst(c);
@@ -2418,11 +2302,11 @@ int ag_bidder_update(ag_ctx *c, const ag_shading_samples *s, const int32_t *agen
     nz.stride = 0;
     nz.e0 = 0;
     nz.epochs = noise_epochs;
-    const DrRecords R{b_ctr, b_val, b_gam, b_prop, b_util, b_won};
-    if (int rc = pipe_run(c, pipe_slots, cnt, R, b_eu, d_off, w.counts, pst, nullptr, nz, traces, 3, st)) return rc;
+    const DrRecords R{SR.ctr, SR.val, SR.gam, SR.prop, SR.util, SR.won};
+    if (int rc = pipe_run(c, pipe_slots, cnt, R, SR.eu, SR.d_off, w.counts, pst, nullptr, nz, traces, 3, st)) return rc;
   }
-  if (int rc = launch(P0)) return rc;
-  if (int rc = launch(P1)) return rc;
+  if (int rc = train_launch(c, P0, D, SR, noise, noise_epochs, traces, st)) return rc;
+  if (int rc = train_launch(c, P1, D, SR, noise, noise_epochs, traces, st)) return rc;
   std::vector<int32_t> h(4 * (size_t)N);
   AG_HIP(hipMemcpyAsync(h.data(), d_epochs, sizeof(int32_t) * 4 * N, hipMemcpyDeviceToHost, st));
   AG_HIP(hipStreamSynchronize(st));
@@ -2517,18 +2401,13 @@ int ag_bidder_rp_begin(ag_ctx *c, const ag_shading_samples *s, const int32_t *ag
   // workgroups: one per kRpChunk of an agent's records on this rank, at least one per trained
   // agent (a rank without records of it still steps its state and adds zeros)
   constexpr int64_t kRpChunk = 2048;
-  std::vector<int32_t> nblk(N, 0), blk_agent, blk_rank, bar_off(N, 0);
-  int lines = 0;
-  for (int a = 0; a < N; ++a) {
-    if (!mask[a]) continue;
-    nblk[a] = (int32_t)std::max<int64_t>(1, (cnt[a] + kRpChunk - 1) / kRpChunk);
-    bar_off[a] = lines;
-    lines += std::max(1, agcoop::bar_lines(nblk[a]));
-    for (int r = 0; r < nblk[a]; ++r) {
-      blk_agent.push_back(a);
-      blk_rank.push_back(r);
-    }
-  }
+  BlockTables T;
+  T.nblk.assign(N, 0);
+  for (int a = 0; a < N; ++a)
+    if (mask[a]) T.nblk[a] = (int32_t)std::max<int64_t>(1, (cnt[a] + kRpChunk - 1) / kRpChunk);
+  block_tables(T, [](int nb) { return std::max(1, agcoop::bar_lines(nb)); });
+  const std::vector<int32_t> &nblk = T.nblk, &blk_agent = T.blk_agent, &blk_rank = T.blk_rank, &bar_off = T.bar_off;
+  const int lines = T.lines;
   const int G = (int)blk_agent.size();
   if ((size_t)G > rp.cap_g || (size_t)lines > rp.cap_lines || !rp.st || !rp.acc || !rp.tables) {
     (void)hipFree(rp.st);
@@ -2668,11 +2547,8 @@ int ag_bidder_rp_epoch(ag_ctx *c, int32_t launches, int64_t *launch_index, float
   hipStream_t st = (hipStream_t)stream;
   ag_dr_ws &w = c->dr;
   ag_dr_rp &rp = w.rp;
-  const int64_t cap = rp.n_local > 0 ? rp.n_local : 1;
-  double *b_ctr = (double *)w.buf;
-  DrRecords R{b_ctr, b_ctr + cap, b_ctr + 2 * cap, b_ctr + 3 * cap, b_ctr + 4 * cap,
-              (const uint8_t *)((uint32_t *)((uint64_t *)(b_ctr + 6 * cap) + 2 * cap) + 2 * cap)};
-  double *b_eu = b_ctr + 5 * cap;
+  double *b_eu = nullptr;
+  const DrRecords R = sorted_view(w, rp.n_local, &b_eu);
   int32_t *d_bagent = rp.tables, *d_brank = d_bagent + rp.cap_g, *d_nblk = d_brank + rp.cap_g, *d_baroff = d_nblk + N;
   FitSt *S = (FitSt *)rp.st;
   for (int32_t l = 0; l < launches; ++l) {

@@ -68,6 +68,33 @@ def test_rp_update_equals_persistent_trainer(gpu):
     eng.close()
 
 
+def test_rp_epoch_two_workgroups_equals_persistent_trainer(gpu):
+    """The per-epoch-launch update with every learner's records on TWO workgroups of one rank
+    (the SPECS learners' records laid twice end to end: 2700 .. 2760 each, one workgroup per
+    2048, so chunks of 1350 .. 1380 -- no multiple of the block size): the second workgroup's
+    slice (c0 > 0), the combining tree's non-root arrival and the rsample index base + c0 + j give the
+    persistent trainer's epochs, status and models bit for bit."""
+    bk, modes, state0, recs, _ = _kat_learners(SPECS)
+    N = len(SPECS)
+    for a in range(N):
+        n = len(recs["agent"][a])
+        for f in recs:
+            recs[f][a] = np.concatenate([recs[f][a], recs[f][a]])
+        recs["order"][a] = N * np.arange(2 * n) + a
+        assert 2048 < 2 * n <= 4096 and n % 256  # two workgroups (one per 2048 records), ragged chunks
+    eng = _engine(bk, modes, state0)
+    st = _learner_store(eng, recs)
+    ep, stat = eng.bidder_update(st, None, np.zeros(N, np.int64), 0)
+    state, init = eng.dr_state()
+    assert (stat == 0).all() and (ep[:, 2] > 0).all()
+    eng.set_dr_state(state0, np.zeros(N, np.int32))
+    (ep2, stat2), = _rp_run([eng], [st], np.ones(N, np.int32))
+    state2, init2 = eng.dr_state()
+    assert np.array_equal(ep2, ep) and np.array_equal(stat2, stat)
+    assert np.array_equal(state2, state) and np.array_equal(init2, init)
+    eng.close()
+
+
 @pytest.mark.parametrize("shards", [2, 3])
 def test_rp_sharded_records_equal_one_process(gpu, shards):
     """`shards` ranks (engines on the one GPU, each holding a contiguous part of every agent's
