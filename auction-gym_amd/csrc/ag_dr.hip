@@ -1715,13 +1715,22 @@ __global__ __launch_bounds__(kDrThreads) void k_sh_hist(const int32_t *__restric
     if (s_hist[a]) atomicAdd((unsigned long long *)&counts[a], (unsigned long long)s_hist[a]);
 }
 
-// records in (agent, log order): sort keys agent << 40 | order, gather every field
+// records in (agent, log order): two stable radix sorts, by the whole 64-bit order, then by
+// agent; then every field gathered
 __global__ __launch_bounds__(kDrThreads) void k_sh_keys(ag_shading_samples s, int64_t n, uint64_t *__restrict__ key,
                                                         uint32_t *__restrict__ idx) {
   for (int64_t i = (int64_t)blockIdx.x * kDrThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kDrThreads) {
-    key[i] = ((uint64_t)(uint32_t)s.agent[i] << 40) | (s.order[i] & ((1ull << 40) - 1));
+    key[i] = s.order[i];
     idx[i] = (uint32_t)i;
   }
+}
+
+// the agents of the records idx (in log order): the second sort's keys
+__global__ __launch_bounds__(kDrThreads) void k_sh_agent_keys(const int32_t *__restrict__ agent, int64_t n,
+                                                              const uint32_t *__restrict__ idx,
+                                                              uint32_t *__restrict__ key) {
+  for (int64_t j = (int64_t)blockIdx.x * kDrThreads + threadIdx.x; j < n; j += (int64_t)gridDim.x * kDrThreads)
+    key[j] = (uint32_t)agent[idx[j]];
 }
 
 __global__ __launch_bounds__(kDrThreads) void k_sh_gather(ag_shading_samples s, int64_t n,
@@ -1958,7 +1967,8 @@ static int dr_ws_ready(ag_ctx *c) {
 }
 
 // The learning bidders' records of a store sorted into (agent, log order) in the workspace
-// (radix sort on agent << 40 | order, then every field gathered): cnt / off host [N] / [N + 1];
+// (stable radix sorts on the 64-bit order, then on agent; every field gathered): cnt / off host
+// [N] / [N + 1];
 // SortedRecs: device arrays [n] (eu: the estimated-utility workspace) and d_off [N + 1].
 struct SortedRecs {
   double *ctr, *val, *gam, *prop, *util, *eu;
@@ -1978,11 +1988,16 @@ static int sort_records(ag_ctx *c, const ag_shading_samples *s, std::vector<int6
   int64_t *d_off = w.counts + N;  // [N + 1] offsets
   AG_HIP(hipMemcpyAsync(d_off, off.data(), sizeof(int64_t) * ((size_t)N + 1), hipMemcpyHostToDevice, st));
   if (n >= ((int64_t)1 << 32)) return ag_set_error(AG_ERR_UNSUPPORTED, "learning bidders' update: >= 2^32 records");
-  // radix-sort workspace: keys in/out (8 B), indices in/out (4 B), then hipcub's temp
-  size_t sort_tmp = 0;
+  // radix-sort workspace: keys in/out (8 B), indices in/out (4 B), then hipcub's temp (the
+  // larger of the two sorts')
+  size_t sort_tmp = 0, agent_tmp = 0;
   AG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, (uint64_t *)nullptr, (uint64_t *)nullptr,
                                             (uint32_t *)nullptr, (uint32_t *)nullptr, (int)(n > 0 ? n : 1), 0, 64,
                                             st));
+  AG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, agent_tmp, (uint32_t *)nullptr, (uint32_t *)nullptr,
+                                            (uint32_t *)nullptr, (uint32_t *)nullptr, (int)(n > 0 ? n : 1), 0, 32,
+                                            st));
+  if (agent_tmp > sort_tmp) sort_tmp = agent_tmp;
   const size_t rec_bytes = (size_t)6 * sizeof(double) + 1;
   const size_t need = (size_t)(n > 0 ? n : 1) * (rec_bytes + 24) + sort_tmp + 256;
   if (need > w.buf_bytes) {
@@ -2003,10 +2018,15 @@ static int sort_records(ag_ctx *c, const ag_shading_samples *s, std::vector<int6
     if (!s->order) return ag_set_error(AG_ERR_INVALID, "learning bidders' update: the store needs order");
     hipLaunchKernelGGL(k_sh_keys, dim3(grid_over(n)), dim3(kDrThreads), 0, st, *s, n, k_in, i_in);
     AG_HIP(hipGetLastError());
-    int end_bit = 40;
-    while ((1ll << (end_bit - 40)) < N) ++end_bit;
-    AG_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, sort_tmp, k_in, k_out, i_in, i_out, (int)n, 0, end_bit, st));
-    hipLaunchKernelGGL(k_sh_gather, dim3(grid_over(n)), dim3(kDrThreads), 0, st, *s, n, i_out, b_ctr, b_val, b_gam,
+    AG_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, sort_tmp, k_in, k_out, i_in, i_out, (int)n, 0, 64, st));
+    // i_out: the records by order. Stably by agent (the order keys' space now holds the agent keys)
+    uint32_t *a_in = (uint32_t *)k_in, *a_out = a_in + cap;
+    hipLaunchKernelGGL(k_sh_agent_keys, dim3(grid_over(n)), dim3(kDrThreads), 0, st, s->agent, n, i_out, a_in);
+    AG_HIP(hipGetLastError());
+    int agent_bits = 1;
+    while ((1ll << agent_bits) < N) ++agent_bits;
+    AG_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, agent_tmp, a_in, a_out, i_out, i_in, (int)n, 0, agent_bits, st));
+    hipLaunchKernelGGL(k_sh_gather, dim3(grid_over(n)), dim3(kDrThreads), 0, st, *s, n, i_in, b_ctr, b_val, b_gam,
                        b_prop, b_util, b_won);
     AG_HIP(hipGetLastError());
   }

@@ -456,7 +456,8 @@ typedef struct ag_shading_samples {
   double *propensity;/* dev [capacity]: logging propensity of gamma                      */
   uint8_t *won;      /* dev [capacity]                                                   */
   uint64_t *order;   /* dev [capacity]: (global auction index) * P + slot -- the record's
-                        place in the agent's log order (the DR fit's noise follows it)    */
+                        place in the agent's log order (the DR fit's noise follows it);
+                        all 64 bits count: the updates sort an agent's records by it      */
 } ag_shading_samples;
 
 /* Append the records of EmpiricalShaded and DoublyRobust bidders of one simulated batch of
@@ -495,9 +496,9 @@ int ag_shading_counts(ag_ctx *ctx, const ag_shading_samples *samples, int64_t *c
  * 79-94 -> src/Bidder.py:473-615): win-rate fit, imitation of the logging policy (first
  * update), doubly robust policy fit; afterwards the agents bid from their policies. The
  * store needs ctr, value, propensity, won and order; records are put in each agent's log
- * order (radix sort on agent, order). noise: dev float32, agent a's DR-fit rsample draws
- * at noise[noise_offsets[a] + e * n_a + i] for its i-th record in log order (n_a = its
- * record count, e < noise_epochs); epochs: host int32 [N][3] epochs run per fit
+ * order (stable radix sorts on the 64-bit order, then on agent). noise: dev float32, agent
+ * a's DR-fit rsample draws at noise[noise_offsets[a] + e * n_a + i] for its i-th record in
+ * log order (n_a = its record count, e < noise_epochs); epochs: host int32 [N][3] epochs run per fit
  * (may be NULL); traces: dev float32 [N][3][32768] per-epoch losses (may be NULL).
  * Synchronises. Arithmetic: oracle/ag_oracle_dr.c ora_dr_update. */
 int ag_dr_update(ag_ctx *ctx, const ag_shading_samples *samples, const float *noise,
