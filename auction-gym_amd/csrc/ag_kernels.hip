@@ -213,7 +213,7 @@ __global__ __launch_bounds__(kThreads) void k_generate_noise(uint64_t seed, uint
         gamma_raw[(int64_t)s * B + i] =
             bkind[a] != AG_BIDDER_TRUTHFUL ? gen_shading_raw(c0, c1, s, k0, k1, pg[a], gs[a]) : NAN;
       if (policy_eps)  // the rsample draw of a fitted policy
-        policy_eps[(int64_t)s * B + i] = gen_normal1(c0, c1, 0, 16 + (uint32_t)s, k0, k1);
+        policy_eps[(int64_t)s * B + i] = gen_normal1(c0, c1, 0, gen_stream(kDrawPolicy, s), k0, k1);
       if (ts_noise && (!ts_index || akind[a] == AG_ALLOCATOR_LRTS)) {
         const bool lr = akind[a] == AG_ALLOCATOR_LRTS;
         // dense tiles: pair (s, i) at s*T*64 + i; compact: the LR-TS pair's rank j
@@ -221,7 +221,7 @@ __global__ __launch_bounds__(kThreads) void k_generate_noise(uint64_t seed, uint
         const float *qa = q + (size_t)a * KDo;
         for (int j = 0; j < KDo; j += 4) {
           float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-          if (lr) gen_normals4(c0, c1, (uint32_t)(j >> 2), 4 + (uint32_t)s, k0, k1, z);
+          if (lr) gen_normals4(c0, c1, (uint32_t)(j >> 2), gen_stream(kDrawThompson, s), k0, k1, z);
           float *row = ts_noise + ((pj >> 6) * KDo + j) * 64 + (pj & 63);
           for (int t = 0; t < 4 && j + t < KDo; ++t) row[64 * t] = lr ? z[t] * (1.0f / sqrtf(qa[j + t])) : 0.0f;
         }
@@ -310,8 +310,8 @@ __global__ __launch_bounds__(kThreads) void k_ts_index_write(const int32_t *part
     }
 }
 
-// Synthetic search grids: U(0.1, 1) with 53-bit uniforms, streams 32 + slot (two per
-// Philox block), grid point j of slot s of auction i at (s*128 + j)*B + i.
+// Synthetic search grids: U(0.1, 1) with 53-bit uniforms, stream gen_stream(kDrawGrid, slot)
+// (two per Philox block), grid point j of slot s of auction i at (s*128 + j)*B + i.
 __global__ __launch_bounds__(kThreads) void k_generate_grid(uint64_t seed, uint64_t first, int64_t B, int P,
                                                            double *grid) {
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
@@ -321,7 +321,7 @@ __global__ __launch_bounds__(kThreads) void k_generate_grid(uint64_t seed, uint6
     for (int s = 0; s < P; ++s)
       for (int j = 0; j < 128; j += 2) {
         uint32_t w[4];
-        philox(c0, c1, (uint32_t)(j >> 1), 32 + (uint32_t)s, k0, k1, w);
+        philox(c0, c1, (uint32_t)(j >> 1), gen_stream(kDrawGrid, s), k0, k1, w);
         const double u0 = (double)((((uint64_t)w[0] << 32) | w[1]) >> 11) * 0x1p-53;
         const double u1 = (double)((((uint64_t)w[2] << 32) | w[3]) >> 11) * 0x1p-53;
         grid[((int64_t)s * 128 + j) * B + i] = 0.1 + 0.9 * u0;
@@ -1058,6 +1058,8 @@ int ag_generate(ag_ctx *c, uint64_t seed, uint64_t first, int64_t B, double *ctx
 int ag_generate_search_grid(ag_ctx *c, uint64_t seed, uint64_t first, int64_t B, double *grid, void *stream) {
   if (!c || !grid) return ag_set_error(AG_ERR_INVALID, "ag_generate_search_grid: null argument");
   if (B < 0) return ag_set_error(AG_ERR_INVALID, "ag_generate_search_grid: B < 0");
+  if (c->shape.num_participants > kGenMaxSlots)  // gen_stream (ag_philox.h) has streams for 64 slots
+    return ag_set_error(AG_ERR_UNSUPPORTED, "ag_generate_search_grid: P > %d", kGenMaxSlots);
   if (B == 0) return AG_OK;
   AgDeviceGuard g(c->device);
   const int grid_n = grid_for(B, (int64_t)1 << 40);
@@ -1071,6 +1073,8 @@ int ag_generate_noise(ag_ctx *c, uint64_t seed, uint64_t first, int64_t B, const
                       double *gamma_raw, float *ts_noise, float *policy_eps, void *stream) {
   if (!c || !part) return ag_set_error(AG_ERR_INVALID, "ag_generate_noise: null argument");
   if (B < 0) return ag_set_error(AG_ERR_INVALID, "ag_generate_noise: B < 0");
+  if (c->shape.num_participants > kGenMaxSlots)
+    return ag_set_error(AG_ERR_UNSUPPORTED, "ag_generate_noise: P > %d", kGenMaxSlots);
   if (B == 0) return AG_OK;
   if (ts_noise && !c->lrts_loaded) return ag_set_error(AG_ERR_STATE, "ag_generate_noise: ag_load_lrts first");
   AgDeviceGuard g(c->device);
@@ -1117,6 +1121,8 @@ int ag_generate_ts_noise_compact(ag_ctx *c, uint64_t seed, uint64_t first, int64
                                  const int32_t *index, float *ts_noise, void *stream) {
   if (!c || !part || !index || !ts_noise) return ag_set_error(AG_ERR_INVALID, "ag_generate_ts_noise_compact: null argument");
   if (B < 0) return ag_set_error(AG_ERR_INVALID, "ag_generate_ts_noise_compact: B < 0");
+  if (c->shape.num_participants > kGenMaxSlots)
+    return ag_set_error(AG_ERR_UNSUPPORTED, "ag_generate_ts_noise_compact: P > %d", kGenMaxSlots);
   if (B == 0) return AG_OK;
   if (!c->lrts_loaded) return ag_set_error(AG_ERR_STATE, "ag_generate_ts_noise_compact: ag_load_lrts first");
   AgDeviceGuard g(c->device);

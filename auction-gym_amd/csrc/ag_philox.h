@@ -28,12 +28,45 @@ __device__ __forceinline__ void philox(uint32_t c0, uint32_t c1, uint32_t c2, ui
   o[3] = c3;
 }
 
-// One synthetic auction (ag_generate; fused into k_oracle's generate mode): Philox4x32-10
-// keyed by seed, counter = (global auction index, block, stream). Stream 0, block 0: u ~ U[0,1)
-// with 53 bits from words 0-1, the first two participants (Floyd's algorithm, slot order =
-// insertion order) from words 2-3; later picks from stream 1, four per call. The context
+// The counter scheme of the synthetic inputs: key = the seed (low, high word), counter =
+// (global auction index low, high word, block, stream). gen_stream is the one place that says
+// which stream a draw kind and slot s < 64 use; tests/gen_reference.py states the same table
+// and checks that no two draws of an auction share a (block, stream):
+//   kind       stream                          blocks
+//   uniform    0                               0 (words 0-1: u; words 2-3: the first two picks)
+//   picks      1                               (t - 2) / 4 of pick step t >= 2    (<= 16 blocks)
+//   context    2                               m / 2 of Box-Muller pair m         (<= 4 blocks)
+//   shading    3                               s
+//   Thompson   4 + s (s < 12),   64 + s above  c / 4 of coefficient c             (<= 16 blocks)
+//   policy     16 + s (s < 12), 128 + s above  0
+//   grid       32 + s (s < 12), 192 + s above  j / 2 of grid point j              (64 blocks)
+// Slots 0..11 have the streams they always had. The slots from 12 up once continued base + s,
+// into the next kind's streams (slot 12's Thompson block 0 was slot 0's policy draw); they now
+// have ranges of their own, 76..127, 140..191 and 204..255. The host refuses P > 64.
+enum GenDraw : uint32_t {
+  kDrawUniform,
+  kDrawPicks,
+  kDrawContext,
+  kDrawShading,
+  kDrawThompson,
+  kDrawPolicy,
+  kDrawGrid
+};
+constexpr int kGenWideSlot = 12, kGenMaxSlots = 64;
+__device__ __forceinline__ uint32_t gen_stream(GenDraw kind, int s = 0) {
+  if (kind <= kDrawShading) return (uint32_t)kind;
+  const uint32_t k = (uint32_t)kind - kDrawThompson;  // 0, 1, 2
+  const uint32_t base = k == 0 ? 4u : k == 1 ? 16u : 32u;
+  return (s < kGenWideSlot ? base : 64u * (k + 1)) + (uint32_t)s;
+}
+
+// One synthetic auction (ag_generate; fused into k_oracle's generate mode). Stream 0, block 0:
+// u ~ U[0,1) with 53 bits from words 0-1, the first two participants (Floyd's algorithm, slot
+// order = insertion order) from words 2-3; later picks from stream 1, four per call. The context
 // (stream 2, two Box-Muller pairs per call): normals z ~ N(0, 1) from 32-bit uniforms in
-// float32 -- the hardware log2 / sqrt / sin / cos (v_sin_f32(t) = sin(2 pi t)), |z| <= 6.7 --,
+// float32 -- u1 = float32((a + 1) 2^-32) in (0, 1], t = float32(w) 2^-32 in [0, 1] (the top 128
+// words round to u1 = 1, r = 0, and to t = 1), the hardware log2 / sqrt / sin / cos
+// (v_sin_f32(t) = sin(2 pi t)), |z| <= 6.7 --,
 // ctx = scale * z (numpy normal(0, scale) in distribution; tests check it). Round 5: 3
 // Philox calls per SP_Oracle auction instead of 5 and no FP64 log / sincos (the generate mode
 // was VALU-bound on them). oracle/ag_oracle.c ora_gen_* restate u and the participants bit
@@ -47,7 +80,7 @@ __device__ __forceinline__ void gen_auction(uint32_t k0, uint32_t k1, uint64_t i
                                             double scale, double (&x)[MAXE], int (&part)[MAXP], double &u) {
   const uint32_t c0 = (uint32_t)idx, c1 = (uint32_t)(idx >> 32);
   uint32_t w[4], v[4];
-  philox(c0, c1, 0, 0, k0, k1, w);
+  philox(c0, c1, 0, gen_stream(kDrawUniform), k0, k1, w);
   u = (double)((((uint64_t)w[0] << 32) | w[1]) >> 11) * 0x1p-53;
   for (int j = N - P; j < N; ++j) {
     const int step = j - (N - P);
@@ -55,7 +88,7 @@ __device__ __forceinline__ void gen_auction(uint32_t k0, uint32_t k1, uint64_t i
     if (step < 2) {
       word = w[2 + step];
     } else {
-      if (((step - 2) & 3) == 0) philox(c0, c1, (uint32_t)((step - 2) >> 2), 1, k0, k1, v);
+      if (((step - 2) & 3) == 0) philox(c0, c1, (uint32_t)((step - 2) >> 2), gen_stream(kDrawPicks), k0, k1, v);
       word = v[(step - 2) & 3];
     }
     int pick = (int)(((uint64_t)word * (uint64_t)(j + 1)) >> 32);
@@ -67,7 +100,7 @@ __device__ __forceinline__ void gen_auction(uint32_t k0, uint32_t k1, uint64_t i
     part[step] = pick;
   }
   for (int m = 0; 2 * m < E; ++m) {
-    if ((m & 1) == 0) philox(c0, c1, (uint32_t)(m >> 1), 2, k0, k1, v);
+    if ((m & 1) == 0) philox(c0, c1, (uint32_t)(m >> 1), gen_stream(kDrawContext), k0, k1, v);
     const float r = gen_normal_r(v[2 * (m & 1)]);
     const float t = (float)v[2 * (m & 1) + 1] * 0x1p-32f;  // [0, 1]
     x[2 * m] = 0.0 + scale * (double)(r * __builtin_amdgcn_cosf(t));
@@ -78,11 +111,11 @@ __device__ __forceinline__ void gen_auction(uint32_t k0, uint32_t k1, uint64_t i
 // Synthetic per-participant draws (ag_generate_noise writes them; the general kernel's generate
 // mode draws the same bits in place). Same key and counter scheme, stream by kind and slot s:
 //  - LR-TS Thompson noise (torch.normal(0, 1/sqrt(q)), src/Models.py:31): coefficient c of slot
-//    s from block c / 4 of stream 4 + s, four float32 normals per Philox call (two Box-Muller
+//    s from block c / 4 of stream gen_stream(kDrawThompson, s), four float32 normals per Philox call (two Box-Muller
 //    pairs from 32-bit uniforms, the hardware transcendentals, as the contexts above; round 6:
 //    before, one FP64 pair per call -- 30 calls and 30 FP64 log / sincos per slot), times
 //    1 / sqrtf(q) of the coefficient;
-//  - a fitted policy's rsample draw: the first normal of block 0 of stream 16 + s;
+//  - a fitted policy's rsample draw: the first normal of block 0 of gen_stream(kDrawPolicy, s);
 //  - shading draws N(prev_gamma, sigma) (numpy normal(loc, scale), src/Bidder.py:51, :177):
 //    prev_gamma + sigma * the first normal of block s of stream 3 (round 6: float32 Box-Muller;
 //    before, an FP64 pair -- its log / sincospi held ~100 VGPRs in the generate-mode kernel).
@@ -106,5 +139,5 @@ __device__ __forceinline__ float gen_normal1(uint32_t c0, uint32_t c1, uint32_t 
 }
 __device__ __forceinline__ double gen_shading_raw(uint32_t c0, uint32_t c1, int s, uint32_t k0, uint32_t k1,
                                                   double prev_gamma, double sigma) {
-  return prev_gamma + sigma * (double)gen_normal1(c0, c1, (uint32_t)s, 3, k0, k1);
+  return prev_gamma + sigma * (double)gen_normal1(c0, c1, (uint32_t)s, gen_stream(kDrawShading), k0, k1);
 }

@@ -470,7 +470,7 @@ struct TsSrc {
   const float *nz;   // HBM: coefficient c at nz[c * 64] (NULL: no noise)
   const float *rsq;  // generate mode: the agent's 1 / sqrtf(q) [K][Do] (NULL: no noise)
   GenKey key;
-  uint32_t stream;   // generate mode: 4 + slot
+  uint32_t stream;   // generate mode: gen_stream(kDrawThompson, slot)
   // AG_TS_DMA: the wave's LDS ring of kTsDmaBufs item buffers (DOS rows of 64 floats each),
   // its LDS byte address, and the batch's item count K (wave-uniform: the DMA schedule)
   const float *ring;
@@ -890,7 +890,7 @@ __device__ __forceinline__ SlotResult resolve_slot(const Lds &T, int K, const do
   // at ((s*T + i/64)*K*Do + c)*64 + i%64; the compact layout tiles the batch's LR-TS pairs
   // only, pair j = ts_noise_index[s*B + i] in place of s*T*64 + i -- mixed populations: no
   // noise stored or fetched for the slots of other agents)
-  TsSrc nz{nullptr, nullptr, gk, 4u + (uint32_t)s};
+  TsSrc nz{nullptr, nullptr, gk, gen_stream(kDrawThompson, s)};
   if constexpr (GENERAL) {
     const int Do = DOS > 0 ? DOS : T.ts_do;
     if constexpr (GEN) {
@@ -957,7 +957,7 @@ __device__ __forceinline__ SlotResult resolve_slot(const Lds &T, int K, const do
         g = 1.0;
         prop = 1.0;
       } else {
-        const float eps = GEN ? gen_normal1(gk.c0, gk.c1, 0, 16u + (uint32_t)s, gk.k0, gk.k1)
+        const float eps = GEN ? gen_normal1(gk.c0, gk.c1, 0, gen_stream(kDrawPolicy, s), gk.k0, gk.k1)
                               : in.policy_eps[(size_t)s * B + i];
         policy_bid(T.drs + a * T.drs_stride + 4, est, v, eps, T.tab, g, prop);
         b = b * g;
@@ -1529,7 +1529,7 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
         for (int s = 0; s < P; ++s) {
           if (polx[s] >= 0) {
             double g, pr;
-            const float eps = GEN ? gen_normal1(gk.c0, gk.c1, 0, 16u + (uint32_t)s, gk.k0, gk.k1)
+            const float eps = GEN ? gen_normal1(gk.c0, gk.c1, 0, gen_stream(kDrawPolicy, s), gk.k0, gk.k1)
                                   : ldg(in.policy_eps + (size_t)s * B + i);
             policy_bid(T.drs + PV[s][0] * T.drs_stride + 4, estv[s], valv[s], eps, T.tab, g, pr);
             gmv[s] = g;
@@ -1550,7 +1550,7 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
               reinterpret_cast<double *>(slots)[64 + t] = valv[s];
               reinterpret_cast<int32_t *>(slots + 1024)[t] = PV[s][0];
               reinterpret_cast<float *>(slots + 1280)[t] =
-                  GEN ? gen_normal1(gk.c0, gk.c1, 0, 16u + (uint32_t)s, gk.k0, gk.k1)
+                  GEN ? gen_normal1(gk.c0, gk.c1, 0, gen_stream(kDrawPolicy, s), gk.k0, gk.k1)
                       : ldg(in.policy_eps + (size_t)s * B + i);
             }
           }

@@ -316,15 +316,23 @@ int ag_generate(ag_ctx *ctx, uint64_t seed, uint64_t first_auction, int64_t B, d
  * shading bidders (NaN otherwise), ts_noise (tiled as in ag_batch_in) = z * (1 / sqrtf(q)) for
  * LR-TS agents (0 otherwise), policy_eps [P][B] = z for every slot; any output may be NULL.
  * Same Philox key / counter scheme; z are float32 Box-Muller normals from 32-bit uniforms, four
- * per Philox call (round 6; before, one FP64 pair per call). */
-/* Synthetic search grids gamma_grid [P][128][B] (U(0.1, 1), Philox as ag_generate_noise,
- * unsorted: the search takes the smallest gamma among tied maxima) for every slot. */
-int ag_generate_search_grid(ag_ctx *ctx, uint64_t seed, uint64_t first_auction, int64_t B, double *gamma_grid,
-                            void *stream);
-
+ * per Philox call (round 6; before, one FP64 pair per call). Counter = (auction index low,
+ * high, block, stream): the shading draw of slot s is the first normal of block s of stream 3;
+ * Thompson coefficient c is normal c % 4 of block c / 4 of stream 4 + s (s < 12) or 64 + s;
+ * policy_eps is the first normal of block 0 of stream 16 + s (s < 12) or 128 + s -- no two
+ * draws of an auction share a (block, stream) (csrc/ag_philox.h gen_stream; slots from 12 up
+ * once ran into the next kind's streams). P <= 64, otherwise AG_ERR_UNSUPPORTED (this and
+ * ag_generate_ts_noise_compact). */
 int ag_generate_noise(ag_ctx *ctx, uint64_t seed, uint64_t first_auction, int64_t B,
                       const int32_t *part, double *gamma_raw, float *ts_noise, float *policy_eps,
                       void *stream);
+
+/* Synthetic search grids gamma_grid [P][128][B] (U(0.1, 1), Philox as ag_generate_noise,
+ * unsorted: the search takes the smallest gamma among tied maxima) for every slot: points
+ * 2b, 2b + 1 of slot s are 0.1 + 0.9 u of the two 53-bit uniforms of block b of stream 32 + s
+ * (s < 12) or 192 + s. P <= 64, otherwise AG_ERR_UNSUPPORTED. */
+int ag_generate_search_grid(ag_ctx *ctx, uint64_t seed, uint64_t first_auction, int64_t B, double *gamma_grid,
+                            void *stream);
 
 /* Compact Thompson-noise layout (ag_batch_in.ts_noise_index, ABI 16): index dev int32 [P][B]
  * = the rank of each LR-TS pair (slot s, auction i) among the batch's LR-TS pairs in
