@@ -350,7 +350,7 @@ def columns_from_records(recs):
 
 
 def _fx(x):
-    """The kernels' per-record rounding (ag_sim.h to_fx): x * 2^36 to nearest-even as an
+    """The kernels' per-record rounding (ag_sim.h fx_add): x * 2^36 to nearest-even as an
     integer, terms with |x| >= 2^26 (or non-finite) dropped."""
     x = np.asarray(x, np.float64)
     ok = np.abs(x) < 2.0 ** 26
@@ -368,10 +368,13 @@ def log_counter_terms(cols, charged, first_price):
     val, bid, tru, est, bev = (cols[k] for k in ("value", "bid", "true_ctr", "est_ctr", "best_ev"))
     lp = cols["price"] if charged else np.zeros(n)
     tv = tru * val
+    with np.errstate(divide="ignore", invalid="ignore"):  # equal bit for bit counts 1 (include/auctiongym.h AG_FX_*)
+        e64, t64 = np.ascontiguousarray(est, np.float64), np.ascontiguousarray(tru, np.float64)
+        bias = np.where(e64.view(np.int64) == t64.view(np.int64), 1.0, e64 / t64)
     t = {C["allocation_regret"]: _fx(bev - tv), C["estimation_regret"]: _fx(est * val - tv),
          C["underbid_regret"]: _fx(((lp - bid) * (lp < tv).astype(np.float64))[~won]),
          C["ctr_sqerr"]: _fx((tru - est) * (tru - est)), C["best_ev_sum"]: _fx(bev),
-         C["ctr_bias_sum"]: _fx((est / np.where(won, tru, 1.0))[won]),
+         C["ctr_bias_sum"]: _fx(bias[won]),
          C["n_logs"]: n << _lib.FX_FRAC_BITS, C["n_won"]: int(won.sum()) << _lib.FX_FRAC_BITS,
          C["overbid_regret"]: _fx((lp - cols["second_price"])[won]) if first_price else 0}
     return t

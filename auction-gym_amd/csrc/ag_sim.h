@@ -6,6 +6,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "auctiongym.h"
 #include "ag_exp.h"
 #include "ag_exp_table.h"
@@ -99,7 +101,9 @@ constexpr int kMidThreads = 768;
 constexpr int kGenOracle = 0, kGenAll = 1, kGenTruthful = 2;
 constexpr int kC = AG_NUM_COUNTERS;
 // Auctions one block may resolve per launch: 1024 per counter replica keeps every replica's
-// int64 sum exact (<= 1024 * P terms of magnitude < 2^50, to_fx).
+// int64 sum exact (<= 1024 * P additions of magnitude <= 2^50 each: fx_add sends the high half
+// of a larger term to the pair's own word, which takes <= 1024 * replicas halves of magnitude
+// <= 2^20 each).
 constexpr int kAuctionsPerReplica = 1024;
 constexpr int kMinGrid = 2048;             // 256 CUs x 8
 constexpr int kMaxSimGrid = 2048;          // partial-sum workspace (>= resident blocks)
@@ -148,14 +152,42 @@ __device__ __forceinline__ int bernoulli(double p, double u) {
   return u > p ? 0 : 1;
 }
 
-// Round x * 2^36 to the nearest integer (ties-to-even), exactly.
-__device__ __forceinline__ unsigned long long to_fx(double x) {
+// One counter term: x * 2^36 rounded to the nearest integer (ties-to-even), exactly, and added
+// to the term's LDS words. |x| < 2^14 (every term of an everyday catalogue): one atomic on the
+// lane's replica `cell`, a term of magnitude <= 2^50. 2^14 <= |x| < 2^26: the term (< 2^62) goes
+// in as two halves, v = lo + hi * 2^42 -- lo in [0, 2^42) to the same cell, hi (|hi| <= 2^20) to
+// the (slot, agent) pair's wide word, which the write-out adds to the pair's high limb. So no
+// cell ever receives a term beyond 2^50, whatever range is admitted. |x| >= 2^26 or not finite:
+// dropped. NZ: zero terms issue no atomic. wide_word() gives the pair's wide word; it is called
+// on the cold path only, so nothing of it is computed or kept for the everyday term.
+template <bool NZ, class WideWord>
+__device__ __forceinline__ void fx_add(unsigned long long *cell, WideWord wide_word, double x) {
+  unsigned long long v;
   if (fabs(x) < 0x1p14) {
-    double y = fma(x, kFxScale, kMagic);
-    return (unsigned long long)(__double_as_longlong(y) - __double_as_longlong(kMagic));
+    const double y = fma(x, kFxScale, kMagic);
+    v = (unsigned long long)(__double_as_longlong(y) - __double_as_longlong(kMagic));
+  } else {  // the cold path: one more atomic, then the common one below
+    // non-finite / absurd term: dropped
+    const long long t = !(fabs(x) < 0x1p26) ? 0ll : (long long)rint(x * kFxScale);
+    if (t != 0ll) atomicAdd(wide_word(), (unsigned long long)(t >> AG_FX_LIMB_BITS));
+    v = (unsigned long long)(t & kLimbMask);
   }
-  if (!(fabs(x) < 0x1p26)) return 0ull;  // non-finite / absurd term: dropped
-  return (unsigned long long)(long long)rint(x * kFxScale);
+  if (!NZ || v != 0ull) atomicAdd(cell, v);
+}
+
+// fx_add for a term known to be below 2^14 in magnitude: the one atomic, no branch.
+template <bool NZ>
+__device__ __forceinline__ void fx_add_small(unsigned long long *cell, double x) {
+  const double y = fma(x, kFxScale, kMagic);
+  const unsigned long long v = (unsigned long long)(__double_as_longlong(y) - __double_as_longlong(kMagic));
+  if (!NZ || v != 0ull) atomicAdd(cell, v);
+}
+
+// AG_C_CTR_BIAS term of a won record: est_ctr / true_ctr, and exactly 1 when the two are equal
+// bit for bit (0 / 0 included: an OracleAllocator's record always counts 1, which is what
+// CTR_BIAS = N_WON of the Oracle builds states).
+__device__ __forceinline__ double ctr_bias_term(double est, double ctr) {
+  return __double_as_longlong(est) == __double_as_longlong(ctr) ? 1.0 : est / ctr;
 }
 
 // LDS carve of k_simulate (all pieces 16-B aligned; offsets in bytes).
@@ -183,7 +215,7 @@ __host__ inline int32_t align16(int64_t b) { return (int32_t)((b + 15) & ~(int64
 //   general populations only: 6 ALLOC_REGRET, 7 EST_REGRET, 8 CTR_SQERR, 9 CTR_BIAS.
 // Derived at write-out: NET = GROSS - PAID. For OracleAllocator + TruthfulBidder
 // populations the general slots are identically 0 (estimated CTR == true CTR and best_ev
-// == true_ctr * value bit for bit) and CTR_BIAS == N_WON (est/true == 1): not accumulated.
+// == true_ctr * value bit for bit) and CTR_BIAS == N_WON (ctr_bias_term == 1): not accumulated.
 constexpr int kOracleSlots = 6;
 constexpr int kGeneralSlots = 10;
 enum { kSlotGross = 0, kSlotPaid, kSlotOverbid, kSlotUnderbid, kSlotBestEv, kSlotCounts,
@@ -244,7 +276,8 @@ __host__ inline LdsLayout make_layout(int N, int K, int D, bool counters, bool g
   L.kag = align16(b);
   b = L.kag + (general ? (int64_t)N * 4 : 0);
   L.cnt = align16(b);
-  b = L.cnt + (counters ? (int64_t)R * N * L.ncnt * 8 : 0);
+  // ... followed by one word per (slot, agent): the high halves of terms >= 2^14 (fx_add)
+  b = L.cnt + (counters ? (int64_t)(R + 1) * N * L.ncnt * 8 : 0);
   L.tsr = 0;
   if (general && gen) {  // after the counters: the other offsets are those of the replay layout
     L.tsr = align16(b);
@@ -1120,7 +1153,7 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
   }
   const int R = L.replicas;
   if (prm.want_counters)
-    for (int i = tid; i < R * N * L.ncnt; i += BT) s_cnt[i] = 0ull;
+    for (int i = tid; i < (R + 1) * N * L.ncnt; i += BT) s_cnt[i] = 0ull;
   __syncthreads();
 
   Lds T{s_tab, s_items, s_vals, s_scr, s_scr_val, s_amax, L.items_stride, L.values_stride,
@@ -1203,77 +1236,100 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
   // register each; flushed to the LDS counters once, after the loop.
   const bool packed = P > 0 && N <= 8 && kAuctionsPerReplica * R / BT <= 255;
   uint64_t n_logs_packed = 0, n_won_packed = 0;
+  // term x of slot j for agent a: to the lane's replica and, for its rare high half, the pair's word
+  auto add_term = [&](auto nz, int j, int a, double x) {
+    // the wide words [slot][agent] follow the R * N * ncnt replica cells
+    fx_add<decltype(nz)::value>(s_cnt + ((size_t)(j * N + a) * R + rep),
+                                [&] { return s_cnt + ((size_t)R * N * prm.lds.ncnt + (j * N + a)); }, x);
+  };
+  // The fixed-point terms of one log record, given as terms(add_raw, add_nz) -- add_nz skips zero
+  // terms (a wave whose lanes all hold 0 issues no atomic). One test per record, not per term:
+  // unless some term of the record reaches 2^14 (never, for an everyday catalogue) every term takes
+  // fx_add_small; otherwise the whole record goes through fx_add, once, in a block of its own.
+  // (From three participants on. With one or two the record's few terms go through fx_add one by
+  // one: on bench.py's population lines the test per record cost 2 % at P = 2 and won 2-6 % at
+  // P = 8, six alternating runs each; HISTORY.md, "exact counters at their edges", has the figures.)
+  auto emit_terms = [&](int a, auto terms) {
+    if constexpr (P == 1 || P == 2) {
+      terms([&](int j, double x) { add_term(std::false_type{}, j, a, x); },
+            [&](int j, double x) { add_term(std::true_type{}, j, a, x); });
+      return;
+    }
+    bool wide = false;
+    auto probe = [&](int, double x) { wide |= !(fabs(x) < 0x1p14); };
+    terms(probe, probe);
+    if (wide) {
+      terms([&](int j, double x) { add_term(std::false_type{}, j, a, x); },
+            [&](int j, double x) { add_term(std::true_type{}, j, a, x); });
+    } else {
+      terms([&](int j, double x) { fx_add_small<false>(s_cnt + ((size_t)(j * N + a) * R + rep), x); },
+            [&](int j, double x) { fx_add_small<true>(s_cnt + ((size_t)(j * N + a) * R + rep), x); });
+    }
+  };
   // the counter terms of one participant (src/Agent.py:96-118, via the exact LDS replicas)
   auto count_slot = [&](int a, bool won, double lp, double price, double second, double bid, double ctr,
                         double val, double est, double bev, int oc) {
-    // [slot j][agent a][replica]: lane-private replicas, conflict-free 8-B atomics
-    auto add_raw = [&](int j, unsigned long long v) { atomicAdd(s_cnt + ((size_t)(j * N + a) * R + rep), v); };
-    // zero terms are skipped (a wave whose lanes all hold 0 issues no atomic): no clicks
-    // for GROSS, and under SecondPrice with P == 2 the loser's underbid term
-    // (price - bid) * [...] is exactly 0 because the price is its bid
-    auto add_nz = [&](int j, unsigned long long v) {
-      if (v != 0ull) add_raw(j, v);
-    };
+    // [slot j][agent a][replica]: lane-private replicas, conflict-free 8-B atomics.
+    // Zero terms are skipped: no clicks for GROSS, and under SecondPrice with P == 2 the loser's
+    // underbid term (price - bid) * [...] is exactly 0 because the price is its bid
     const double tv = ctr * val;
-    if (won) {
-      add_nz(kSlotGross, to_fx(val * (double)oc));
-      add_raw(kSlotPaid, to_fx(price));
-      if (prm.mech == AG_FIRST_PRICE) add_nz(kSlotOverbid, to_fx(lp - second));
-    } else {
-      add_nz(kSlotUnderbid, to_fx((lp - bid) * (double)(lp < tv)));
-    }
-    add_raw(kSlotBestEv, to_fx(bev));
+    emit_terms(a, [&](auto add_raw, auto add_nz) {
+      if (won) {
+        add_nz(kSlotGross, val * (double)oc);
+        add_raw(kSlotPaid, price);
+        if (prm.mech == AG_FIRST_PRICE) add_nz(kSlotOverbid, lp - second);
+      } else {
+        add_nz(kSlotUnderbid, (lp - bid) * (double)(lp < tv));
+      }
+      add_raw(kSlotBestEv, bev);
+      if constexpr (GENERAL) {  // src/Agent.py:96-118 terms that vanish for Oracle agents
+        add_nz(kSlotAlloc, bev - tv);
+        add_nz(kSlotEst, est * val - tv);
+        const double dd = ctr - est;
+        add_nz(kSlotSqerr, dd * dd);
+        if (won) add_raw(kSlotBias, ctr_bias_term(est, ctr));
+      }
+    });
     if (packed) {  // 8-bit per-agent fields in registers, flushed once per block
       const uint64_t bit = 1ull << (8 * a);
       n_logs_packed += bit;
       if (won) n_won_packed += bit;
     } else {
-      add_raw(kSlotCounts, won ? 0x100000001ull : 1ull);
-    }
-    if constexpr (GENERAL) {  // src/Agent.py:96-118 terms that vanish for Oracle agents
-      add_nz(kSlotAlloc, to_fx(bev - tv));
-      add_nz(kSlotEst, to_fx(est * val - tv));
-      const double dd = ctr - est;
-      add_nz(kSlotSqerr, to_fx(dd * dd));
-      if (won) add_raw(kSlotBias, to_fx(est / ctr));
+      atomicAdd(s_cnt + ((size_t)(kSlotCounts * N + a) * R + rep), won ? 0x100000001ull : 1ull);
     }
   };
   // count_slot in two parts (the same exact integer terms, added in another order): the
   // terms that do not depend on the auction's winner as soon as a slot is resolved, so the
   // slot's CTRs / best EV need not stay live while the other slots are resolved ...
   auto count_pre = [&](int a, double ctr, double val, double est, double bev) {
-    auto add_raw = [&](int j, unsigned long long v) { atomicAdd(s_cnt + ((size_t)(j * N + a) * R + rep), v); };
-    auto add_nz = [&](int j, unsigned long long v) {
-      if (v != 0ull) add_raw(j, v);
-    };
     const double tv = ctr * val;
-    add_raw(kSlotBestEv, to_fx(bev));
-    add_nz(kSlotAlloc, to_fx(bev - tv));
-    add_nz(kSlotEst, to_fx(est * val - tv));
-    const double dd = ctr - est;
-    add_nz(kSlotSqerr, to_fx(dd * dd));
+    emit_terms(a, [&](auto add_raw, auto add_nz) {
+      add_raw(kSlotBestEv, bev);
+      add_nz(kSlotAlloc, bev - tv);
+      add_nz(kSlotEst, est * val - tv);
+      const double dd = ctr - est;
+      add_nz(kSlotSqerr, dd * dd);
+    });
   };
-  // ... and the rest once the winner and price are known (tv = ctr * val, ratio = est / ctr)
+  // ... and the rest once the winner and price are known (tv = ctr * val, ratio = ctr_bias_term(est, ctr))
   auto count_post = [&](int a, bool won, double lp, double price, double second, double bid, double tv,
                         double val, double ratio, int oc) {
-    auto add_raw = [&](int j, unsigned long long v) { atomicAdd(s_cnt + ((size_t)(j * N + a) * R + rep), v); };
-    auto add_nz = [&](int j, unsigned long long v) {
-      if (v != 0ull) add_raw(j, v);
-    };
-    if (won) {
-      add_nz(kSlotGross, to_fx(val * (double)oc));
-      add_raw(kSlotPaid, to_fx(price));
-      if (prm.mech == AG_FIRST_PRICE) add_nz(kSlotOverbid, to_fx(lp - second));
-      add_raw(kSlotBias, to_fx(ratio));
-    } else {
-      add_nz(kSlotUnderbid, to_fx((lp - bid) * (double)(lp < tv)));
-    }
+    emit_terms(a, [&](auto add_raw, auto add_nz) {
+      if (won) {
+        add_nz(kSlotGross, val * (double)oc);
+        add_raw(kSlotPaid, price);
+        if (prm.mech == AG_FIRST_PRICE) add_nz(kSlotOverbid, lp - second);
+        add_raw(kSlotBias, ratio);
+      } else {
+        add_nz(kSlotUnderbid, (lp - bid) * (double)(lp < tv));
+      }
+    });
     if (packed) {
       const uint64_t bit = 1ull << (8 * a);
       n_logs_packed += bit;
       if (won) n_won_packed += bit;
     } else {
-      add_raw(kSlotCounts, won ? 0x100000001ull : 1ull);
+      atomicAdd(s_cnt + ((size_t)(kSlotCounts * N + a) * R + rep), won ? 0x100000001ull : 1ull);
     }
   };
 #if AG_PREFETCH
@@ -1437,7 +1493,7 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
           w = s;
           ctr_w = q.ctr;
           val_w = q.val;
-          rat_w = q.est / q.ctr;
+          rat_w = ctr_bias_term(q.est, q.ctr);
         } else if (q.bid > m2) {
           m2 = q.bid;
         }
@@ -1502,7 +1558,7 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
         bidv[s] = q.bid;
         valv[s] = q.val;
         tvv[s] = q.ctr * q.val;
-        ratv[s] = q.est / q.ctr;
+        ratv[s] = ctr_bias_term(q.est, q.ctr);
         ctrv[s] = q.ctr;
         estv[s] = q.est;
         gmv[s] = q.gamma;
@@ -1722,6 +1778,7 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
           slo += l;
           shi += h;
         }
+        shi += (long long)s_cnt[(size_t)R * pairs + pr];  // the high halves of the pair's terms >= 2^14 (0 for the counts)
         s_cnt[(size_t)pr * R] = (unsigned long long)slo;
         s_cnt[(size_t)pr * R + 1] = (unsigned long long)shi;
       }
@@ -1740,6 +1797,7 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
           hi[j] = (long long)s_cnt[(size_t)pr * R + 1];
         } else {
           split(pr, s_cnt[pr], lo[j], hi[j]);
+          hi[j] += (long long)s_cnt[(size_t)R * pairs + pr];
         }
         if (j == kSlotCounts) {
           nlogs = (unsigned long long)lo[j];

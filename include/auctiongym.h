@@ -106,7 +106,25 @@ typedef enum ag_counter {
  * so results are independent of grid size, block order, batch split and GPU count.
  * Limb arrays can be summed across GPUs with an int64 all-reduce and then normalised.
  * AG_C_NET is held as AG_C_GROSS - AG_C_PAID (each record's net term value*outcome -
- * price is then rounded as two terms). */
+ * price is then rounded as two terms).
+ *
+ * The limits (tests/counter_reference.py states them in plain integers, tests/test_gpu_counters.py
+ * takes every simulate kernel to them):
+ *  - Admitted terms: a term x with |x| < 2^26 contributes round(x * 2^36), ties to even, whatever
+ *    its size within that range and however many such terms a launch sums.
+ *  - Dropped terms: a term with |x| >= 2^26, or one that is not finite, contributes 0 -- that term
+ *    alone: the record's other counters still get theirs (a GROSS term of 2^26 is dropped while
+ *    the PAID and BEST_EV terms below it are kept).
+ *  - Normal form: limbs 0 and 1 in [0, 2^42), limb 2 signed and carrying the sign of the total
+ *    (-1 is (2^42 - 1, 2^42 - 1, -1)). Every ag_simulate / ag_simulate_generated call leaves all
+ *    N * AG_NUM_COUNTERS counters in normal form.
+ *  - A buffer that is not in normal form may be accumulated into (limbs summed over ranks and not
+ *    yet normalised, say): its value limb0 + limb1 * 2^42 + limb2 * 2^84 is kept and the result is
+ *    normalised, provided |limb0|, |limb1| < 2^62 and the total fits the three limbs.
+ *  - AG_C_CTR_BIAS: a won record contributes est_ctr / true_ctr, and exactly 1 when the two are the
+ *    same double bit for bit -- 0 / 0 (a true CTR that underflowed to 0) included. So an
+ *    OracleAllocator's counter always equals its AG_C_N_WON. est_ctr / 0 otherwise is not finite
+ *    and is dropped. (The reference reports NaN for the whole iteration in either case.) */
 #define AG_FX_FRAC_BITS 36
 #define AG_FX_LIMB_BITS 42
 #define AG_FX_LIMBS 3

@@ -305,7 +305,8 @@ static void simulate_range(const ora_pop *pp, const double *items, const double 
         t[ORA_C_GROSS] = last_value;
         t[ORA_C_N_WON] = 1.0;
         t[ORA_C_PAID] = pr;
-        t[ORA_C_CTR_BIAS] = est_ctr[o] / true_ctr[o];
+        /* equal bit for bit counts exactly 1 (0 / 0 included: include/auctiongym.h AG_FX_*) */
+        t[ORA_C_CTR_BIAS] = memcmp(&est_ctr[o], &true_ctr[o], sizeof(double)) ? est_ctr[o] / true_ctr[o] : 1.0;
       }
       t[ORA_C_ALLOC_REGRET] = out->best_ev[o] - tv;
       t[ORA_C_EST_REGRET] = est_ctr[o] * value[o] - tv;

@@ -194,12 +194,15 @@ def _population(pop, N):
     return ak, bk, init, modes
 
 
-def _general_setup(seed, N, P, K, E, OE, mech, pop, sample=True, ragged=False, B=549):
-    """Engine + host inputs + the oracle's answer for a general population of any shape."""
+def _general_setup(seed, N, P, K, E, OE, mech, pop, sample=True, ragged=False, B=549, catalogue=None):
+    """Engine + host inputs + the oracle's answer for a general population of any shape. catalogue:
+    (items, values) to use instead of the suite's recipe (the generator's draws stay the same)."""
     from auctiongym_amd.engine import AuctionEngine
     g = np.random.default_rng(seed)
     Do = OE + 1
     items, values = _catalogue(g, N, K, E)
+    if catalogue is not None:
+        items, values = catalogue
     ak, bk, init, modes = _population(pop, N)
     pg, gs = 0.5 + 0.5 * g.random(N), 0.01 + 0.05 * g.random(N)
     m = g.normal(0, 1, (N, K, Do)).astype(np.float32)
