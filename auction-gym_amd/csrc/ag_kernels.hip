@@ -369,16 +369,20 @@ SimKernel pick_kernel(int P, int D, bool prune, int W, int general, int bt) {
   }
 }
 
-OraKernel pick_oracle(int P, int D, bool gen) {
+// k_oracle for a shape; with an output set (ora_field_mask) that has a specialised build
+// (ag_sim_p.hip), that build, and *spec true. fields = 0: the run-time form.
+OraKernel pick_oracle(int P, int D, bool gen, uint32_t fields = 0, bool *spec = nullptr) {
+  bool unused;
+  if (!spec) spec = &unused;
   switch (P) {
-    case 1: return pick_oracle_for<1>(D, gen);
-    case 2: return pick_oracle_for<2>(D, gen);
-    case 3: return pick_oracle_for<3>(D, gen);
-    case 4: return pick_oracle_for<4>(D, gen);
-    case 5: return pick_oracle_for<5>(D, gen);
-    case 6: return pick_oracle_for<6>(D, gen);
-    case 7: return pick_oracle_for<7>(D, gen);
-    case 8: return pick_oracle_for<8>(D, gen);
+    case 1: return pick_oracle_for<1>(D, gen, fields, spec);
+    case 2: return pick_oracle_for<2>(D, gen, fields, spec);
+    case 3: return pick_oracle_for<3>(D, gen, fields, spec);
+    case 4: return pick_oracle_for<4>(D, gen, fields, spec);
+    case 5: return pick_oracle_for<5>(D, gen, fields, spec);
+    case 6: return pick_oracle_for<6>(D, gen, fields, spec);
+    case 7: return pick_oracle_for<7>(D, gen, fields, spec);
+    case 8: return pick_oracle_for<8>(D, gen, fields, spec);
     default: return nullptr;
   }
 }
@@ -396,8 +400,9 @@ int resident_blocks(const ag_ctx *c, const void *k, size_t lds, int *out) {
   return AG_OK;
 }
 
-// ag_simulate for OracleAllocator + TruthfulBidder populations: k_oracle (ag_sim_oracle.h).
-int simulate_oracle(ag_ctx *c, OraKernel k, int64_t B, const ag_batch_in *in, const ag_batch_out *out,
+// ag_simulate for OracleAllocator + TruthfulBidder populations: k_oracle (ag_sim_oracle.h). The
+// caller has checked that pick_oracle has a kernel for the shape.
+int simulate_oracle(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch_out *out,
                     int64_t *counters_fx, hipStream_t st, uint64_t seed = 0, uint64_t first = 0) {
   const ag_shape &s = c->shape;
   OraParams prm;
@@ -427,23 +432,31 @@ int simulate_oracle(ag_ctx *c, OraKernel k, int64_t B, const ag_batch_in *in, co
   prm.winner_outcome = out->winner_outcome;
   prm.partials = c->d_partials;
   prm.queue = c->d_queue;
+  // the build with this call's output set compile-time, where there is one (same results)
+  bool is_spec = false;
+  const OraKernel k = pick_oracle(s.num_participants, c->D, in == nullptr, ora_field_mask(prm), &is_spec);
+  // k_oracle forms a row's offset e * B in 32 bits (and adds the auction index in 64): the
+  // last ctx row must start below 2^32. B * P < 2^31 gives that from P = 2 up to D = 6
+  if (in && (int64_t)(c->D - 2) * B > (int64_t)UINT32_MAX)
+    return ag_set_error(AG_ERR_UNSUPPORTED, "ag_simulate: (D - 2) * B must be < 2^32 (32-bit row offsets); "
+                        "split the batch");
   const size_t lds = (size_t)prm.L.total;
   if (lds > 160 * 1024)
     return ag_set_error(AG_ERR_UNSUPPORTED, "ag_simulate: population needs %zu B of LDS (> 160 KiB)", lds);
   if (lds > 64 * 1024)
     AG_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  int &res_max = c->resident_ora[(prm.want_counters ? 1 : 0) + (in ? 0 : 2)];
+  int &res_max = c->resident_ora[(prm.want_counters ? 1 : 0) + (in ? 0 : 2) + (is_spec ? 4 : 0)];
   if (res_max == 0)
     if (int rc = resident_blocks(c, (const void *)k, lds, &res_max)) return rc;
-  // Persistent grid of kOraBlocksPerCu workgroups per CU, capped by residency
-  // (AG_OPT_SIM_BLOCKS_PER_CU overrides). With the static stride fewer than the 5 the
-  // registers allow streamed better (round 4: 4 per CU 0.473 ms vs 5 per CU 0.503 ms); with
-  // the work counters (AG_ORA_QUEUE) all 5 do (3.57 -> 3.41 ms per 2^27, r05zm_ab_sub_bpc.log)
+  // Persistent grid, capped by residency (AG_OPT_SIM_BLOCKS_PER_CU overrides): as many
+  // workgroups per CU as fit for the run-time form (kOraBlocksPerCu; 5 at P = 2, D = 6, in
+  // generate mode too: 4.02 -> 3.87 ms per 2^27 auctions, profiles/r05w_ab_gen.log), and
+  // kOraSpecBlocksPerCu for the specialised builds: the grid they were measured at, at P = 2
+  // (HBM inputs -5 %, generate mode -1 %, profiles/r07_bench_full_compare.txt); at other P
+  // the specialised builds and their grid are not measured (ag_sim_oracle.h)
   int res = res_max;
   {
-    // generate mode (no input stream, VALU-heavier): as many as fit (5 at 87 VGPRs) --
-    // 4.02 -> 3.87 ms per 2^27 auctions (profiles/r05w_ab_gen.log)
-    const int per_cu = c->grid_per_cu > 0 ? c->grid_per_cu : (in ? kOraBlocksPerCu : 8);
+    const int per_cu = c->grid_per_cu > 0 ? c->grid_per_cu : (is_spec ? kOraSpecBlocksPerCu : kOraBlocksPerCu);
     int cus = 0;
     AG_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
     if ((int64_t)per_cu * cus < res) res = per_cu * cus;
@@ -969,6 +982,9 @@ int ag_simulate(ag_ctx *c, int64_t B, const ag_batch_in *in, ag_batch_out *out_a
   if (B < 0) return ag_set_error(AG_ERR_INVALID, "ag_simulate: B < 0");
   if (B == 0) return AG_OK;
   if (!in->ctx || !in->part || !in->u) return ag_set_error(AG_ERR_INVALID, "ag_simulate: null input array");
+  // The kernels index a stream as base + row + i, with row (a multiple of B) and i < B each
+  // widened to 64 bits before the add: row + i may pass 2^32 in ctx (row up to (D - 2) * B)
+  // and is never formed in 32 bits; what this bounds is every row of the P-row arrays
   if (B * c->shape.num_participants > INT32_MAX)
     return ag_set_error(AG_ERR_UNSUPPORTED, "ag_simulate: B * P must be < 2^31 (32-bit SoA indexing); "
                      "split the batch");
@@ -988,8 +1004,8 @@ int ag_simulate(ag_ctx *c, int64_t B, const ag_batch_in *in, ag_batch_out *out_a
   if (c->vl_any_search && !in->gamma_grid)
     return ag_set_error(AG_ERR_INVALID, "ag_simulate: ValueLearningBidders bidding by search need gamma_grid");
   if (prune && !c->general && c->ora_catalog && c->sim_kernel != AG_SIM_KERNEL_GENERIC && !c->wide)
-    if (OraKernel ok = pick_oracle(s.num_participants, D, false))
-      return simulate_oracle(c, ok, B, in, out, counters_fx, (hipStream_t)stream);
+    if (pick_oracle(s.num_participants, D, false))
+      return simulate_oracle(c, B, in, out, counters_fx, (hipStream_t)stream);
   return simulate_general(c, B, in, out, counters_fx, (hipStream_t)stream, false, 0, 0);
 }
 
@@ -1035,7 +1051,7 @@ int ag_simulate_generated(ag_ctx *c, uint64_t seed, uint64_t first, int64_t B, a
                         kMaxP, 2 * kMaxKPairs, kOraMaxValue);
   AgDeviceGuard g(c->device);
   // a launch covers auctions [lo, hi) of the batch: their global indices are first + lo ...
-  return simulate_oracle(c, k, B, nullptr, out, counters_fx, (hipStream_t)stream, seed, first);
+  return simulate_oracle(c, B, nullptr, out, counters_fx, (hipStream_t)stream, seed, first);
 }
 
 int ag_generate(ag_ctx *c, uint64_t seed, uint64_t first, int64_t B, double *ctx_out, int32_t *part_out,

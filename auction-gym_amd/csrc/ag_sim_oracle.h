@@ -63,11 +63,24 @@ constexpr double kOraMaxValue = 1024.0;
 #ifndef AG_ORA_STORE_LATE
 #define AG_ORA_STORE_LATE 1  // every per-slot output stored after the slots, field by field (A/B: 0 stores each slot's as it resolves; 3.73 -> 3.59 ms per 2^27, profiles/r05h_ab_packed.log)
 #endif
+#ifndef AG_ORA_SPECIALISE
+// k_oracle builds with the output set compile-time (FM below) for the headline's set; the host
+// picks them per call (pick_oracle_for) and runs them at kOraSpecBlocksPerCu workgroups per CU,
+// identical results. 4.6 / 0.2 / 4.9 / 5.6 % faster per 2^27 auctions at P = 2 in four runs
+// (profiles/r07_ab_specialise.log, step2@4 of runs 3-4, step2 of run 7, new of run 8). A/B:
+// make variant-p VP=2 VFLAGS=-DAG_ORA_SPECIALISE=0
+#define AG_ORA_SPECIALISE 1
+#endif
 constexpr int kOraFlush = 255;
-// default persistent grid (ag_kernels.hip simulate_oracle): as many workgroups as fit (5 per CU
-// at 85 VGPRs). With the static stride 4 streamed better than 5 (the blocks drift apart); with
-// the work counters 5 per CU is 4.7 % faster than 4 (profiles/r05zm_ab_sub_bpc.log)
+// default persistent grid (ag_kernels.hip simulate_oracle). Run-time form: a cap above what the
+// registers allow, so as many workgroups as fit -- 5 per CU (89 VGPRs at P = 2, D = 6). With
+// the static stride 4 streamed better than 5 (the blocks drift apart); with the work counters
+// it is 4.7 % faster at 5 per CU than at 4 (profiles/r05zm_ab_sub_bpc.log). The specialised
+// builds are the other way round: at 5 per CU they lose 2.4 % to the run-time form, at 4 per CU
+// they win (profiles/r07_ab_specialise.log, runs 1, 3, 4, 7, 8; P = 2 only, other P not
+// measured). Their registers (91 VGPRs at P = 2) would allow 5, so their 4 is set here
 constexpr int kOraBlocksPerCu = 8;
+constexpr int kOraSpecBlocksPerCu = 4;
 __host__ inline int64_t ora_lane_cap(int R) { return 512 * (int64_t)R; }
 
 struct OraLayout {
@@ -126,6 +139,25 @@ struct OraParams {
   double scale;          // embedding_var
 };
 
+// The output arrays of a call as a bit set: k_oracle's FM. 0 is the run-time form (each
+// pointer tested where it is stored); kOraHeadline is the benchmark's set
+// (engine.HEADLINE_FIELDS: the packed winner word, no winner / outcome / second_price).
+constexpr uint32_t kOraFWinner = 1, kOraFPrice = 2, kOraFSecondPrice = 4, kOraFOutcome = 8, kOraFItem = 16,
+                   kOraFBid = 32, kOraFEstCtr = 64, kOraFTrueCtr = 128, kOraFBestEv = 256, kOraFWinnerOutcome = 512;
+constexpr uint32_t kOraHeadline =
+    kOraFWinnerOutcome | kOraFPrice | kOraFItem | kOraFBid | kOraFEstCtr | kOraFTrueCtr | kOraFBestEv;
+__host__ inline uint32_t ora_field_mask(const OraParams &p) {
+  return (p.winner ? kOraFWinner : 0) | (p.price ? kOraFPrice : 0) | (p.second_price ? kOraFSecondPrice : 0) |
+         (p.outcome ? kOraFOutcome : 0) | (p.item ? kOraFItem : 0) | (p.bid ? kOraFBid : 0) |
+         (p.est_ctr ? kOraFEstCtr : 0) | (p.true_ctr ? kOraFTrueCtr : 0) | (p.best_ev ? kOraFBestEv : 0) |
+         (p.winner_outcome ? kOraFWinnerOutcome : 0);
+}
+// Is output field BIT written? Compile-time under a field set FM, else the pointer's null test.
+template <uint32_t FM, uint32_t BIT>
+__device__ __forceinline__ bool ora_has(const void *p) {
+  if constexpr (FM != 0) return (FM & BIT) != 0;
+  else return p != nullptr;
+}
 // Branch-free x * 2^36 rounded to nearest-even for |x| < 2^14 (kOraMaxValue bounds it).
 __device__ __forceinline__ unsigned long long ora_fx(double x) {
   const double y = fma(x, kFxScale, kMagic);
@@ -177,7 +209,9 @@ __device__ __forceinline__ uint32_t ora_screen_one(const float *__restrict__ row
 // GEN = false: inputs read from HBM (replay / the HBM-resident synthetic batches).
 // GEN = true: inputs drawn in the kernel by gen_auction (ag_philox.h), the same bits as
 // ag_generate writes; nothing is read from HBM but the catalogue.
-template <int P, int D, bool GEN>
+// FM: 0, or the call's output set as a compile-time bit set (kOraF*): the stores of a tile
+// are then one basic block, not a null test and a drained counter per field. Same results.
+template <int P, int D, bool GEN, uint32_t FM = 0>
 __global__ __launch_bounds__(kThreads) void k_oracle(OraParams prm) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int N = prm.N, K = prm.K;
@@ -296,6 +330,8 @@ __global__ __launch_bounds__(kThreads) void k_oracle(OraParams prm) {
 #else
   for (uint32_t i = lo + blockIdx.x * kThreads + tid; i < hi; i += stride) {
 #endif
+    // element row + i of a stream (row: a multiple of B)
+    auto at = [&](auto *base, uint32_t row) { return base + row + i; };
     double x[kMaxD];
     float xf[kMaxD];
     float xabs = 1.0f;
@@ -320,10 +356,10 @@ __global__ __launch_bounds__(kThreads) void k_oracle(OraParams prm) {
       }
 #else
 #pragma unroll
-      for (int e = 0; e < D - 1; ++e) x[e] = ldg(prm.ctx + e * B + i);
+      for (int e = 0; e < D - 1; ++e) x[e] = ldg(at(prm.ctx, e * B));
 #pragma unroll
-      for (int s = 0; s < P; ++s) ag[s] = ldg(prm.part + s * B + i);
-      u = ldg(prm.u + i);
+      for (int s = 0; s < P; ++s) ag[s] = ldg(at(prm.part, s * B));
+      u = ldg(at(prm.u, 0));
 #endif
     }
 #pragma unroll
@@ -382,12 +418,11 @@ __global__ __launch_bounds__(kThreads) void k_oracle(OraParams prm) {
       bdv[s] = b;
       ctv[s] = c;
 #else
-      const uint32_t o = s * B + i;
-      if (prm.item) stg(prm.item + o, (int32_t)best);
-      if (prm.bid) stg(prm.bid + o, b);
-      if (prm.est_ctr) stg(prm.est_ctr + o, c);
-      if (prm.true_ctr) stg(prm.true_ctr + o, c);
-      if (prm.best_ev) stg(prm.best_ev + o, sc);
+      if (ora_has<FM, kOraFItem>(prm.item)) stg(at(prm.item, s * B), (int32_t)best);
+      if (ora_has<FM, kOraFBid>(prm.bid)) stg(at(prm.bid, s * B), b);
+      if (ora_has<FM, kOraFEstCtr>(prm.est_ctr)) stg(at(prm.est_ctr, s * B), c);
+      if (ora_has<FM, kOraFTrueCtr>(prm.true_ctr)) stg(at(prm.true_ctr, s * B), c);
+      if (ora_has<FM, kOraFBestEv>(prm.best_ev)) stg(at(prm.best_ev, s * B), sc);
 #endif
       // streaming top-2, ties -> lowest slot (src/AuctionAllocation.py:19-34)
       if (s == 0) {
@@ -410,25 +445,25 @@ __global__ __launch_bounds__(kThreads) void k_oracle(OraParams prm) {
     // every per-slot output after the slots, field by field
 #pragma unroll
     for (int s = 0; s < P; ++s)
-      if (prm.item) stg(prm.item + s * B + i, (int32_t)itv[s]);
+      if (ora_has<FM, kOraFItem>(prm.item)) stg(at(prm.item, s * B), (int32_t)itv[s]);
 #pragma unroll
     for (int s = 0; s < P; ++s)
-      if (prm.bid) stg(prm.bid + s * B + i, bdv[s]);
+      if (ora_has<FM, kOraFBid>(prm.bid)) stg(at(prm.bid, s * B), bdv[s]);
 #pragma unroll
     for (int s = 0; s < P; ++s)
-      if (prm.est_ctr) stg(prm.est_ctr + s * B + i, ctv[s]);
+      if (ora_has<FM, kOraFEstCtr>(prm.est_ctr)) stg(at(prm.est_ctr, s * B), ctv[s]);
 #pragma unroll
     for (int s = 0; s < P; ++s)
-      if (prm.true_ctr) stg(prm.true_ctr + s * B + i, ctv[s]);
+      if (ora_has<FM, kOraFTrueCtr>(prm.true_ctr)) stg(at(prm.true_ctr, s * B), ctv[s]);
 #pragma unroll
     for (int s = 0; s < P; ++s)
-      if (prm.best_ev) stg(prm.best_ev + s * B + i, bevs[s]);
+      if (ora_has<FM, kOraFBestEv>(prm.best_ev)) stg(at(prm.best_ev, s * B), bevs[s]);
 #endif
-    if (prm.winner) stg(prm.winner + i, (int32_t)w);
-    if (prm.price) stg(prm.price + i, charged ? price : (double)NAN);
-    if (prm.second_price) stg(prm.second_price + i, charged ? m2 : (double)NAN);
-    if (prm.outcome) stg(prm.outcome + i, (uint8_t)oc);
-    if (prm.winner_outcome) stg(prm.winner_outcome + i, pack_wo(w, oc));
+    if (ora_has<FM, kOraFWinner>(prm.winner)) stg(at(prm.winner, 0), (int32_t)w);
+    if (ora_has<FM, kOraFPrice>(prm.price)) stg(at(prm.price, 0), charged ? price : (double)NAN);
+    if (ora_has<FM, kOraFSecondPrice>(prm.second_price)) stg(at(prm.second_price, 0), charged ? m2 : (double)NAN);
+    if (ora_has<FM, kOraFOutcome>(prm.outcome)) stg(at(prm.outcome, 0), (uint8_t)oc);
+    if (ora_has<FM, kOraFWinnerOutcome>(prm.winner_outcome)) stg(at(prm.winner_outcome, 0), pack_wo(w, oc));
 
     if (prm.want_counters) {
 #pragma unroll
@@ -549,17 +584,19 @@ __global__ __launch_bounds__(kThreads) void k_oracle(OraParams prm) {
 
 typedef void (*OraKernel)(OraParams);
 
-// Defined per P in ag_sim_p.hip: k_oracle<P, D, gen> for D in [2, 8].
+// Defined per P in ag_sim_p.hip: k_oracle<P, D, gen> for D in [2, 8]; for an output set
+// fields (ora_field_mask) that has one, the build with it compile-time and *spec true
+// (fields = 0: always the run-time form).
 template <int P>
-OraKernel pick_oracle_for(int D, bool gen);
-template <> OraKernel pick_oracle_for<0>(int, bool);
-template <> OraKernel pick_oracle_for<1>(int, bool);
-template <> OraKernel pick_oracle_for<2>(int, bool);
-template <> OraKernel pick_oracle_for<3>(int, bool);
-template <> OraKernel pick_oracle_for<4>(int, bool);
-template <> OraKernel pick_oracle_for<5>(int, bool);
-template <> OraKernel pick_oracle_for<6>(int, bool);
-template <> OraKernel pick_oracle_for<7>(int, bool);
-template <> OraKernel pick_oracle_for<8>(int, bool);
+OraKernel pick_oracle_for(int D, bool gen, uint32_t fields, bool *spec);
+template <> OraKernel pick_oracle_for<0>(int, bool, uint32_t, bool *);
+template <> OraKernel pick_oracle_for<1>(int, bool, uint32_t, bool *);
+template <> OraKernel pick_oracle_for<2>(int, bool, uint32_t, bool *);
+template <> OraKernel pick_oracle_for<3>(int, bool, uint32_t, bool *);
+template <> OraKernel pick_oracle_for<4>(int, bool, uint32_t, bool *);
+template <> OraKernel pick_oracle_for<5>(int, bool, uint32_t, bool *);
+template <> OraKernel pick_oracle_for<6>(int, bool, uint32_t, bool *);
+template <> OraKernel pick_oracle_for<7>(int, bool, uint32_t, bool *);
+template <> OraKernel pick_oracle_for<8>(int, bool, uint32_t, bool *);
 
 }  // namespace ag

@@ -46,7 +46,10 @@ SimKernel pick_kernel_for<0>(int D, bool prune, int W, int general, int bt) {
 }
 
 template <>
-OraKernel pick_oracle_for<0>(int, bool) { return nullptr; }
+OraKernel pick_oracle_for<0>(int, bool, uint32_t, bool *spec) {
+  *spec = false;
+  return nullptr;
+}
 #else
 template <>
 SimKernel pick_kernel_for<AG_P>(int D, bool prune, int W, int general, int bt) {
@@ -98,8 +101,16 @@ SimKernel pick_kernel_for<AG_P>(int D, bool prune, int W, int general, int bt) {
 }
 
 template <>
-OraKernel pick_oracle_for<AG_P>(int D, bool gen) {
+OraKernel pick_oracle_for<AG_P>(int D, bool gen, uint32_t fields, bool *spec) {
   constexpr int P = AG_P;
+  *spec = false;
+#if AG_ORA_SPECIALISE
+  // the headline shape's output set (E = 5; bench.py's fields): every field test compile-time
+  if (D == 6 && fields == kOraHeadline) {
+    *spec = true;
+    return gen ? k_oracle<P, 6, true, kOraHeadline> : k_oracle<P, 6, false, kOraHeadline>;
+  }
+#endif
   switch (D) {
     case 2: return gen ? k_oracle<P, 2, true> : k_oracle<P, 2, false>;
     case 3: return gen ? k_oracle<P, 3, true> : k_oracle<P, 3, false>;
