@@ -220,7 +220,7 @@ class AuctionEngine:
     def set_simulate_kernel(self, generic):
         """generic=True: always the general simulate kernel (k_simulate); False (default):
         k_oracle for OracleAllocator + TruthfulBidder populations, k_simulate for the others;
-        "wide": the runtime-P kernel at any P (A/B variant builds only). Identical results."""
+        "wide": the runtime-P kernel at any P, a retired experiment the library refuses. Identical results."""
         mode = {"wide": _lib.SIM_KERNEL_WIDE}.get(generic) or (
             _lib.SIM_KERNEL_GENERIC if generic else _lib.SIM_KERNEL_AUTO)
         self._check(self.L.ag_set_option(self._h, _lib.OPT_SIMULATE_KERNEL, mode), "ag_set_option")

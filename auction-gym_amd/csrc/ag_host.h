@@ -140,13 +140,12 @@ struct ag_ctx {
   int64_t *d_partials = nullptr;
   uint32_t *d_queue = nullptr;  // k_oracle's chunk counters (AG_ORA_QUEUE): 64 x 32 words
   int32_t partial_blocks = 0;
-  int32_t resident_wide[2] = {};  // the AG_SIM_KERNEL_WIDE A/B kernel's [counters]
-  int32_t resident[512] = {};  // resident blocks [generate mode][768 lanes][shipped shape][truthful-only][768 / 1024 lanes][general][W][screened][counters]
+  int32_t resident[256] = {};  // resident blocks [generate mode][768 lanes][shipped shape][truthful-only][768 / 1024 lanes][general][screened][counters]
   bool ship_shape = true;      // AG_OPT_SIM_SHIPPED_SHAPE: the compile-time shipped-shape general build
   bool gen_mode_all = false;   // AG_OPT_SIM_GENERAL_MODE = 1: the full general build for every population
   int64_t launch_cap = 0;  // AG_OPT_LAUNCH_AUCTIONS
   int64_t lrts_chunk = 0;  // AG_OPT_LRTS_BLOCK_SAMPLES
-  bool wide = false;  // 1 auction per lane by default: higher occupancy, faster when sustained
+  bool wide = false;  // AG_OPT_LANE_AUCTIONS = 2: k_simulate (one auction per lane) for Oracle populations too
   bool catalog = false;
   bool values_positive = false;  // every catalogue value > 0: the f32 item screens apply
   bool ora_catalog = false;  // catalogue within k_oracle's bounds (ag_sim_oracle.h)

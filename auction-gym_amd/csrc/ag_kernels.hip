@@ -31,10 +31,6 @@
 #include "ag_sim.h"
 #include "ag_sim_oracle.h"
 
-#ifndef AG_SIM_WIDE_AB
-#define AG_SIM_WIDE_AB 0  // AG_SIM_KERNEL_WIDE (the runtime-P kernel at any P): A/B variant builds only
-#endif
-
 // ------------------------------------------------------------------------------------
 // error plumbing (declared in ag_host.h)
 // ------------------------------------------------------------------------------------
@@ -354,17 +350,17 @@ __global__ __launch_bounds__(kThreads) void k_stream_copy(const u32x4 *__restric
 // ------------------------------------------------------------------------------------
 // dispatch
 // ------------------------------------------------------------------------------------
-SimKernel pick_kernel(int P, int D, bool prune, int W, int general, int bt) {
-  if (P > kMaxP) return pick_kernel_for<0>(D, prune, W, general, bt);  // runtime-P kernel
+SimKernel pick_kernel(int P, int D, bool prune, int general, int bt) {
+  if (P > kMaxP) return pick_kernel_for<0>(D, prune, general, bt);  // runtime-P kernel
   switch (P) {
-    case 1: return pick_kernel_for<1>(D, prune, W, general, bt);
-    case 2: return pick_kernel_for<2>(D, prune, W, general, bt);
-    case 3: return pick_kernel_for<3>(D, prune, W, general, bt);
-    case 4: return pick_kernel_for<4>(D, prune, W, general, bt);
-    case 5: return pick_kernel_for<5>(D, prune, W, general, bt);
-    case 6: return pick_kernel_for<6>(D, prune, W, general, bt);
-    case 7: return pick_kernel_for<7>(D, prune, W, general, bt);
-    case 8: return pick_kernel_for<8>(D, prune, W, general, bt);
+    case 1: return pick_kernel_for<1>(D, prune, general, bt);
+    case 2: return pick_kernel_for<2>(D, prune, general, bt);
+    case 3: return pick_kernel_for<3>(D, prune, general, bt);
+    case 4: return pick_kernel_for<4>(D, prune, general, bt);
+    case 5: return pick_kernel_for<5>(D, prune, general, bt);
+    case 6: return pick_kernel_for<6>(D, prune, general, bt);
+    case 7: return pick_kernel_for<7>(D, prune, general, bt);
+    case 8: return pick_kernel_for<8>(D, prune, general, bt);
     default: return nullptr;
   }
 }
@@ -542,7 +538,6 @@ int simulate_general(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch
   // fast or faster on every line, P = 8 included once its slots stream -- configs_1 at P = 8
   // 0.665 against 0.680 ms, profiles/r04k_ab_c1p8.log; at P = 2 on every line,
   // profiles/r03_ab_pop_vs_generic.log)
-  int W = (prune && (B % 2) == 0 && c->wide && !c->general && s.num_participants <= kMaxP) ? 2 : 1;
   size_t lds = (size_t)prm.lds.total;
   if (lds > 160 * 1024)
     return ag_set_error(AG_ERR_UNSUPPORTED, "ag_simulate: population needs %zu B of LDS (> 160 KiB)", lds);
@@ -563,14 +558,10 @@ int simulate_general(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch
       s.num_participants <= kMaxP)
     bt = kMidThreads;
   const int genb = gen ? kGenGen : 0;  // generate mode: the shipped shape's GEN builds
-  SimKernel k = pick_kernel(s.num_participants, D, prune, W, gmode | ship | genb, bt);
+  SimKernel k = pick_kernel(s.num_participants, D, prune, gmode | ship | genb, bt);
   if (!k && bt == kMidThreads) {
     bt = kLargeThreads;
-    k = pick_kernel(s.num_participants, D, prune, W, gmode | ship | genb, bt);
-  }
-  if (!k && W == 2) {  // the two-auctions-per-lane build is an A/B variant only (AG_LANE_PAIRS)
-    W = 1;
-    k = pick_kernel(s.num_participants, D, prune, W, gmode | ship | genb, bt);
+    k = pick_kernel(s.num_participants, D, prune, gmode | ship | genb, bt);
   }
   // 1024-lane workgroups asked for by option where no such build exists (they come with the
   // screened item search, P <= kMaxP): an error, not a quiet 256-lane launch
@@ -581,16 +572,8 @@ int simulate_general(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch
                         kLargeThreads, 2 * kMaxKPairs, kMaxP, s.num_participants, D, s.num_items);
   if (!k && bt != kThreads) {
     bt = kThreads;
-    k = pick_kernel(s.num_participants, D, prune, W, gmode | ship | genb, bt);
+    k = pick_kernel(s.num_participants, D, prune, gmode | ship | genb, bt);
   }
-  bool wide_ab = false;
-#if AG_SIM_WIDE_AB
-  if (c->general && c->sim_kernel == AG_SIM_KERNEL_WIDE) {  // the runtime-P kernel at any P (A/B)
-    bt = kThreads;
-    k = pick_kernel_for<0>(D, prune, 1, kGenAll, kThreads);
-    wide_ab = true;
-  }
-#endif
   if (!k && gen)
     return ag_set_error(AG_ERR_UNSUPPORTED,
                         "ag_simulate_generated: general populations in the shipped shape only (E = 5, OE = 4, "
@@ -605,12 +588,9 @@ int simulate_general(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch
   }
   // Persistent grid: exactly the blocks the device keeps resident (no partial last round),
   // each striding over bt-auction tiles.
-  // (the WIDE A/B kernel has slots of its own: its occupancy is not the AUTO kernel's)
-  int &res = wide_ab ? c->resident_wide[prm.want_counters ? 1 : 0]
-                     : c->resident[(gen ? 256 : 0) + (bt == kMidThreads ? 128 : 0) + (ship ? 64 : 0) +
-                                   (gmode == kGenTruthful ? 32 : 0) +
-                                   (bt == kThreads ? 0 : 16) + (c->general ? 8 : 0) + (W == 2 ? 4 : 0) +
-                                   (prune ? 2 : 0) + (prm.want_counters ? 1 : 0)];
+  int &res = c->resident[(gen ? 128 : 0) + (bt == kMidThreads ? 64 : 0) + (ship ? 32 : 0) +
+                         (gmode == kGenTruthful ? 16 : 0) + (bt == kThreads ? 0 : 8) + (c->general ? 4 : 0) +
+                         (prune ? 2 : 0) + (prm.want_counters ? 1 : 0)];
   if (res == 0) {  // first launch of this build: the kernel's static LDS (AG_TS_DMA's noise rings) on top
     hipFuncAttributes fa;
     AG_HIP(hipFuncGetAttributes(&fa, (const void *)k));
@@ -644,7 +624,7 @@ int simulate_general(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch
   if (chunk_max < 2) chunk_max = 2;
   for (int64_t lo = 0; lo < B; lo += chunk_max) {
     const int64_t hi = lo + chunk_max < B ? lo + chunk_max : B;
-    const int64_t tiles = (hi - lo + bt * W - 1) / (bt * W);
+    const int64_t tiles = (hi - lo + bt - 1) / bt;
     const int grid = (int)(tiles < grid_max ? tiles : grid_max);
     prm.lo = (int32_t)lo;
     prm.hi = (int32_t)hi;
@@ -704,7 +684,7 @@ int ag_create(int32_t device, const ag_shape *s, ag_ctx **out) {
   // simulate needs a kernel for (P, D) and the catalogue in LDS; allocate-only contexts
   // (any P) do not.
   const LdsLayout lay = make_layout(s->num_agents, s->num_items, D, true);
-  c->can_simulate = pick_kernel(s->num_participants, D, false, 1, false, kThreads) &&
+  c->can_simulate = pick_kernel(s->num_participants, D, false, false, kThreads) &&
                     lay.total <= 160 * 1024;
   AgDeviceGuard g(device);
   hipError_t e = hipMalloc(&c->d_items, sizeof(double) * s->num_agents * s->num_items * D);
@@ -912,9 +892,9 @@ int ag_set_option(ag_ctx *c, int32_t option, int64_t value) {
       if (value == AG_SIM_KERNEL_FUSED || value == AG_SIM_KERNEL_SPLIT)
         return ag_set_error(AG_ERR_UNSUPPORTED, "ag_set_option: k_pop (AG_SIM_KERNEL_FUSED / SPLIT) was retired in "
                                                 "round 4: k_simulate is as fast on every population line");
-      if (value == AG_SIM_KERNEL_WIDE && !AG_SIM_WIDE_AB)  // the round-3 A/B (2.3x slower): variant builds only
-        return ag_set_error(AG_ERR_UNSUPPORTED, "ag_set_option: AG_SIM_KERNEL_WIDE is built only in the A/B "
-                                                "variant (make variant VFLAGS=-DAG_SIM_WIDE_AB=1)");
+      if (value == AG_SIM_KERNEL_WIDE)
+        return ag_set_error(AG_ERR_UNSUPPORTED, "ag_set_option: AG_SIM_KERNEL_WIDE (the runtime-P kernel at any P) was "
+                                                "a round-3 experiment, 2.3x slower: no longer built");
       c->sim_kernel = (int32_t)value;
       return AG_OK;
     default:

@@ -16,27 +16,11 @@
 
 namespace ag {
 
-// Build knobs (A/B variants, `make variant`): AG_PREFETCH software-pipelines the next
-// tile's input loads; AG_MIN_WAVES caps VGPRs via launch bounds; AG_MAX_REPLICAS caps the
-// per-lane counter replicas (LDS per block).
-#ifndef AG_POLICY_COMPACT
-#define AG_POLICY_COMPACT 1  // early path: fitted-policy bids compacted across the wave's slots
-#endif
-#ifndef AG_EARLY_COUNT
-#define AG_EARLY_COUNT 1  // general kernel: per-slot stores and counter terms as slots resolve
-#endif
-#ifndef AG_STREAM_SYNC
-#define AG_STREAM_SYNC 0  // streamed slots (P >= 3): workgroup barrier per tile (1) or per slot (2), A/B
-#endif
-#ifndef AG_XCD_MAP
-#define AG_XCD_MAP 0  // general kernel: consecutive auction tiles to the workgroups of one XCD (A/B)
-#endif
-#ifndef AG_STREAM_PACK_AGENTS
-#define AG_STREAM_PACK_AGENTS 0  // streamed slots (P >= 3): the counter pass's agents kept packed in registers
-#endif
-#ifndef AG_PREFETCH
-#define AG_PREFETCH 0
-#endif
+// Build knobs (A/B variants, `make variant`): the launch bounds of the general builds (the
+// *_MIN_WAVES below cap VGPRs), the Thompson item choice (AG_TS_SCREEN, AG_TS_GROUP, AG_TS_DMA*),
+// AG_STREAM_MIN_P, AG_MAX_REPLICAS (per-lane counter replicas: LDS per block), AG_LARGE_BT and the
+// diagnostic AG_ABLATE. Experiments that were measured and lost are recorded in HISTORY.md, not
+// kept here as code.
 #ifndef AG_GEN_MIN_WAVES
 #define AG_GEN_MIN_WAVES 3  // the general kernel: <= 168 VGPRs
 #endif
@@ -58,20 +42,18 @@ namespace ag {
 #ifndef AG_TS_SCREEN
 #define AG_TS_SCREEN 1  // screened Thompson item choice (ts_select)
 #endif
-#ifndef AG_MIN_WAVES
-#define AG_MIN_WAVES 1
-#endif
-#ifndef AG_STREAM_GENALL
-#define AG_STREAM_GENALL 0  // A/B: streamed slots for the full mix too (make variant)
-#endif
 #ifndef AG_STREAM_MIN_P
 #define AG_STREAM_MIN_P 3  // general kernel: streamed slots (no per-slot result arrays) from this P on
 #endif
 #ifndef AG_MAX_REPLICAS
 #define AG_MAX_REPLICAS 16
 #endif
+// Diagnostic ablations of the general kernel (WRONG results; make variant-p VFLAGS=-DAG_ABLATE=..):
+// 1 no fitted-policy forward (gamma 1), 2 no Thompson item choice (the true-CTR leader),
+// 4 no exact true-CTR item search (item 0, CTR 0.5), 16 no MAP estimate (0.5), 32 no re-scored
+// true CTR of the Thompson choice (the leader's), 64 the Thompson choice computed but its noise not read
 #ifndef AG_ABLATE
-#define AG_ABLATE 0  // diagnostic ablations of the general kernel (see kAblate below)
+#define AG_ABLATE 0
 #endif
 #ifndef AG_TS_DMA
 #define AG_TS_DMA 1  // replayed Thompson noise streamed into a per-wave LDS ring by LDS-DMA: the
@@ -412,66 +394,19 @@ __device__ __forceinline__ int select_item(const double *__restrict__ itm, const
 // fused simulate kernel
 // ------------------------------------------------------------------------------------
 
-// W-wide SoA accesses (W = 2: one 16-B / 8-B / 2-B access per lane for two auctions).
-// AG_NT_LOADS / AG_NT_STORES: non-temporal streaming of the batch inputs and outputs (each
-// byte is touched once). Measured (tools/ab_libs.py, SP_Oracle shape, 2^24 auctions): 3 %
-// faster back to back than cached accesses (0.501 vs 0.516 ms); on by default.
-#ifndef AG_NT_LOADS
-#define AG_NT_LOADS 1
-#endif
-#ifndef AG_NT_STORES
-#define AG_NT_STORES 1
-#endif
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
+// The batch inputs and outputs stream through non-temporal accesses (each byte is touched once).
+// Measured (tools/ab_libs.py, SP_Oracle shape, 2^24 auctions): 3 % faster back to back than
+// cached accesses (0.501 vs 0.516 ms).
 template <typename T>
 __device__ __forceinline__ T ldg(const T *p) {
-  if constexpr (AG_NT_LOADS) return __builtin_nontemporal_load(p);
-  else return *p;
+  return __builtin_nontemporal_load(p);
 }
 template <typename T>
 __device__ __forceinline__ void stg(T *p, T v) {
-  if constexpr (AG_NT_STORES) __builtin_nontemporal_store(v, p);
-  else *p = v;
+  __builtin_nontemporal_store(v, p);
 }
 // ABI 17: winner and outcome as one word (ag_batch_out.winner_outcome)
 __device__ __forceinline__ uint32_t pack_wo(int w, int oc) { return (uint32_t)w | ((uint32_t)(oc & 1) << 31); }
-
-template <int W>
-__device__ __forceinline__ void ld_f64(const double *p, double (&v)[W]) {
-  if constexpr (W == 1) {
-    v[0] = ldg(p);
-  } else {
-    const f64x2 t = ldg(reinterpret_cast<const f64x2 *>(p));
-    v[0] = t.x;
-    v[1] = t.y;
-  }
-}
-template <int W>
-__device__ __forceinline__ void ld_i32(const int32_t *p, int (&v)[W]) {
-  if constexpr (W == 1) {
-    v[0] = ldg(p);
-  } else {
-    const i32x2 t = ldg(reinterpret_cast<const i32x2 *>(p));
-    v[0] = t.x;
-    v[1] = t.y;
-  }
-}
-template <int W>
-__device__ __forceinline__ void st_f64(double *p, const double (&v)[W]) {
-  if constexpr (W == 1) stg(p, v[0]);
-  else stg(reinterpret_cast<f64x2 *>(p), f64x2{v[0], v[1]});
-}
-template <int W>
-__device__ __forceinline__ void st_i32(int32_t *p, const int (&v)[W]) {
-  if constexpr (W == 1) stg(p, (int32_t)v[0]);
-  else stg(reinterpret_cast<i32x2 *>(p), i32x2{v[0], v[1]});
-}
-template <int W>
-__device__ __forceinline__ void st_u8(uint8_t *p, const int (&v)[W]) {
-  if constexpr (W == 1) stg(p, (uint8_t)v[0]);
-  else stg(reinterpret_cast<uint16_t *>(p), (uint16_t)((v[0] & 1) | ((v[1] & 1) << 8)));
-}
 
 // LDS views of the catalogue + tables for one block
 struct Lds {
@@ -543,15 +478,6 @@ __device__ __forceinline__ void ts_dma_item5(const float *src, uint32_t lds_any)
         "s"(lds + 512u), "s"(lds + 768u), "s"(lds + 1024u)
       : "memory");
 }
-
-// One auction resolved (src/Auction.py:28-74 minus the draws).
-template <int P>
-struct Resolved {
-  int ag[P], item[P];
-  double val[P], bid[P], ctr[P], est[P], bev[P], gamma[P], prop[P];
-  int w, oc;
-  double price, second;
-};
 
 // torch's float32 exp on the CPU as torch.sigmoid's vectorised path computes it (SLEEF's
 // expf_u10; oracle/ag_oracle_dr.c torch_expf bit for bit): q = round(x / ln 2), the reduced
@@ -898,14 +824,7 @@ struct SlotResult {
   bool pol;  // DEFER: a fitted-policy bid left to the caller (bid = value * est, gamma / prop NaN)
 };
 
-// Diagnostic ablations of the general kernel (WRONG results; make variant-p VFLAGS=-DAG_ABLATE=..):
-// 1 no fitted-policy forward (gamma 1), 2 no Thompson item choice (the true-CTR leader),
-// 4 no exact true-CTR item search (item 0, CTR 0.5), 16 no MAP estimate (0.5), 32 no re-scored
-// true CTR of the Thompson choice (the leader's), 64 the Thompson choice computed but its noise not read
-#ifndef AG_ABLATE
-#define AG_ABLATE 0
-#endif
-constexpr int kAblate = AG_ABLATE;
+constexpr int kAblate = AG_ABLATE;  // the diagnostic ablations (top of this file)
 
 // GEN: generate mode -- the slot's draws (Thompson noise, rsample, shading) made here from the
 // auction's Philox counter `gk`, the bits ag_generate_noise stores (ag_philox.h); `in` unread.
@@ -1027,6 +946,15 @@ __device__ __forceinline__ void top2_step(int s, double b, double &m1, double &m
   }
 }
 
+// One auction resolved (src/Auction.py:28-74 minus the draws).
+template <int P>
+struct Resolved {
+  int ag[P], item[P];
+  double val[P], bid[P], ctr[P], est[P], bev[P], gamma[P], prop[P];
+  int w, oc;
+  double price, second;
+};
+
 template <int P, int D, bool PRUNE, int GENERAL, bool GEN = false, int DOS = 0>
 __device__ __forceinline__ void resolve(const Lds &T, int K, int mech, const double (&x)[kMaxD],
                                         const float (&xf)[kMaxD], float xabs, const int (&ag)[P], double u,
@@ -1071,10 +999,10 @@ __device__ __forceinline__ void resolve(const Lds &T, int K, int mech, const dou
 // auction's global index, the bits ag_generate + ag_generate_noise store (contexts,
 // participants, uniform: gen_auction; Thompson noise, rsample and shading draws: resolve_slot);
 // only the outputs touch HBM. Shipped-shape builds (DOS > 0) only.
-template <int P, int D, bool PRUNE, int W, int GENERAL, int BT = kThreads, int DOS = 0, bool GEN = false>
+template <int P, int D, bool PRUNE, int GENERAL, int BT = kThreads, int DOS = 0, bool GEN = false>
 __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_MIN_WAVES : AG_TB_MIN_WAVES)
                                  : (GENERAL ? ((DOS && P > 0 && P <= 2) ? AG_GEN_DOS_MIN_WAVES : AG_GEN_MIN_WAVES)
-                                            : AG_MIN_WAVES)) void k_simulate(SimParams prm) {
+                                            : 1)) void k_simulate(SimParams prm) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int N = prm.N, K = prm.K;
   const uint32_t B = (uint32_t)prm.B;  // SoA leading dimension (auctions in the batch)
@@ -1099,7 +1027,7 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
   // AG_TS_DMA: every wave's Thompson-noise ring (kTsDmaBufs items of 5 rows x 64 floats)
   constexpr bool kDma = AG_TS_DMA && GENERAL && DOS == 5 && !GEN && BT == kThreads && P >= 1 && P <= AG_TS_DMA_MAXP;
   __shared__ __attribute__((aligned(16))) float s_ring[kDma ? (BT / 64) * kTsDmaBufs * 5 * 64 : 1];
-  static_assert(!GEN || (DOS > 0 && P > 0 && W == 1 && GENERAL), "generate mode: shipped-shape general builds");
+  static_assert(!GEN || (DOS > 0 && P > 0 && GENERAL), "generate mode: shipped-shape general builds");
   unsigned long long *s_cnt = reinterpret_cast<unsigned long long *>(smem + L.cnt);
 
   const int tid = threadIdx.x;
@@ -1171,18 +1099,16 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
   const ag_batch_in in = prm.in;
   const ag_batch_out out = prm.out;
   // P == 0: the runtime-P kernel (more than kMaxP participants; slot results are not kept
-  // in registers -- see the wide path in the loop)
+  // in registers -- see the runtime-P path in the loop)
   constexpr int PA = P > 0 ? P : 1;  // register array extent
-  static_assert(P > 0 || !AG_PREFETCH, "the runtime-P path has no software-pipelined loads");
   const bool charged = P == 0 ? prm.P >= 2 : P >= 2;  // P == 1: nobody charged (Auction.py:68)
 
-  // inputs of one tile: the context, participants and uniform of W consecutive auctions
-  double xv[kMaxD][W];
-  int pv[PA][W];
-  double uv[W];
-  int jv[PA][W];  // compact ts_noise_index entries (GENERAL with ts_noise_index; else kTsjLoad)
-  const bool pre_tsj = !GEN && GENERAL && !AG_PREFETCH && in.ts_noise_index && in.ts_noise && prm.ts_sample;
-  static_assert(!GEN || !AG_PREFETCH, "generate mode has no input loads to pipeline");
+  // inputs of one tile: the context, participants and uniform of the lane's auction
+  double xv[kMaxD];
+  int pv[PA];
+  double uv;
+  int jv[PA];  // compact ts_noise_index entries (GENERAL with ts_noise_index; else kTsjLoad)
+  const bool pre_tsj = !GEN && GENERAL && in.ts_noise_index && in.ts_noise && prm.ts_sample;
   const uint32_t gk0 = (uint32_t)prm.seed, gk1 = (uint32_t)(prm.seed >> 32);
   // generate mode: the tile's inputs drawn (ag_generate's bits) instead of loaded
   auto gen_tile = [&](uint32_t i) {
@@ -1190,47 +1116,36 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
     int pk[PA];
     gen_auction<PA, kMaxD>(gk0, gk1, prm.first + i, N, PA, D - 1, prm.scale, x, pk, u);
 #pragma unroll
-    for (int e = 0; e < D - 1; ++e) xv[e][0] = x[e];
+    for (int e = 0; e < D - 1; ++e) xv[e] = x[e];
 #pragma unroll
     for (int s = 0; s < PA; ++s) {
-      pv[s][0] = pk[s];
-      jv[s][0] = kTsjLoad;
+      pv[s] = pk[s];
+      jv[s] = kTsjLoad;
     }
-    uv[0] = u;
+    uv = u;
   };
   // streamed slots (below): each slot's participant / noise index loaded with the slot
   // streamed slots for TruthfulBidder-only populations (configs_1 at P = 8: 0.665 vs 0.730 ms
   // kept per-slot arrays, profiles/r04k_ab_c1p8.log) and for the full mix in its 768-lane build
   // (kMidThreads)
   constexpr bool kStream =
-      (GENERAL == kGenTruthful || (GENERAL == kGenAll && (BT == kMidThreads || AG_STREAM_GENALL))) && W == 1 &&
-      P >= AG_STREAM_MIN_P;
+      (GENERAL == kGenTruthful || (GENERAL == kGenAll && BT == kMidThreads)) && P >= AG_STREAM_MIN_P;
   auto load_tile = [&](uint32_t i) {
 #pragma unroll
-    for (int e = 0; e < D - 1; ++e) ld_f64<W>(in.ctx + e * B + i, xv[e]);
+    for (int e = 0; e < D - 1; ++e) xv[e] = ldg(in.ctx + e * B + i);
     if constexpr (kStream) {
-      ld_f64<W>(in.u + i, uv);
+      uv = ldg(in.u + i);
       return;
     }
 #pragma unroll
-    for (int s = 0; s < P; ++s) ld_i32<W>(in.part + s * B + i, pv[s]);
-    ld_f64<W>(in.u + i, uv);
+    for (int s = 0; s < P; ++s) pv[s] = ldg(in.part + s * B + i);
+    uv = ldg(in.u + i);
 #pragma unroll
     for (int s = 0; s < P; ++s) {
-      if (pre_tsj) {
-        ld_i32<W>(in.ts_noise_index + s * B + i, jv[s]);
-      } else {
-#pragma unroll
-        for (int q = 0; q < W; ++q) jv[s][q] = kTsjLoad;
-      }
+      jv[s] = pre_tsj ? ldg(in.ts_noise_index + s * B + i) : kTsjLoad;
     }
   };
-  const uint32_t stride = gridDim.x * (BT * W);
-  // the workgroup's tile in each grid stride: blockIdx, or with AG_XCD_MAP the workgroups of one
-  // XCD (dispatched round-robin over the 8) on consecutive tiles, so the lines two neighbouring
-  // tiles share (the compact Thompson noise's runs) meet in one L2
-  const uint32_t wg_tile = (AG_XCD_MAP && gridDim.x % 8 == 0) ? (blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8
-                                                               : blockIdx.x;
+  const uint32_t stride = gridDim.x * BT;
   // Participation / win counts: a lane resolves at most kAuctionsPerReplica * R / BT
   // (<= 255) auctions per launch, so for N <= 8 agents its counts fit 8-bit fields of one
   // register each; flushed to the LDS counters once, after the loop.
@@ -1332,36 +1247,10 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
       atomicAdd(s_cnt + ((size_t)(kSlotCounts * N + a) * R + rep), won ? 0x100000001ull : 1ull);
     }
   };
-#if AG_PREFETCH
-  // software pipelining: the next tile's loads are in flight while this tile computes
-  double xn[kMaxD][W];
-  int pn[PA][W];
-  double un[W];
-  if (lo + wg_tile * (BT * W) + tid * W < hi) load_tile(lo + wg_tile * (BT * W) + tid * W);
-#endif
-  for (uint32_t base = lo + wg_tile * (BT * W); base < hi; base += stride) {
-    const uint32_t i = base + tid * W;  // W consecutive auctions (even chunk bounds when W = 2)
+  for (uint32_t base = lo + blockIdx.x * BT; base < hi; base += stride) {
+    const uint32_t i = base + tid;
     // generate mode: the auction's Philox counter (its global index) for the slots' draws
     const GenKey gk{(uint32_t)(prm.first + i), (uint32_t)((prm.first + i) >> 32), gk0, gk1};
-    if constexpr (kStream && AG_STREAM_SYNC == 1) __syncthreads();
-    [[maybe_unused]] const bool wg_full = base + BT * W <= hi;  // uniform over the workgroup
-#if AG_PREFETCH
-    if (i >= hi) continue;
-#pragma unroll
-    for (int e = 0; e < D - 1; ++e)
-#pragma unroll
-      for (int q = 0; q < W; ++q) xn[e][q] = xv[e][q];
-#pragma unroll
-    for (int s = 0; s < P; ++s)
-#pragma unroll
-      for (int q = 0; q < W; ++q) pn[s][q] = pv[s][q];
-#pragma unroll
-    for (int q = 0; q < W; ++q) un[q] = uv[q];
-    if (i + stride < hi) load_tile(i + stride);
-#define XV xn
-#define PV pn
-#define UV un
-#else
     if (i >= hi) continue;
     if constexpr (P == 0) {
       // more than kMaxP participants (runtime P): the slots are resolved in a loop, their
@@ -1423,17 +1312,13 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
       // loads now -- none is left for it to wait for (with a count that cannot see the noise
       // DMAs) once the slots' DMAs are in flight
 #pragma unroll
-      for (int e = 0; e < D - 1; ++e) asm volatile("" ::"v"(xv[e][0]));
-      asm volatile("" ::"v"(uv[0]));
+      for (int e = 0; e < D - 1; ++e) asm volatile("" ::"v"(xv[e]));
+      asm volatile("" ::"v"(uv));
       if constexpr (!kStream) {
 #pragma unroll
-        for (int s = 0; s < PA; ++s) asm volatile("" ::"v"(pv[s][0]), "v"(jv[s][0]));
+        for (int s = 0; s < PA; ++s) asm volatile("" ::"v"(pv[s]), "v"(jv[s]));
       }
     }
-#define XV xv
-#define PV pv
-#define UV uv
-#endif
 
     if constexpr (kStream) {
       // Streamed slots (wide auctions): each slot resolved with its bid made in place (a fitted
@@ -1448,7 +1333,7 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
       float xabs = 1.0f;
 #pragma unroll
       for (int e = 0; e < D - 1; ++e) {
-        x[e] = XV[e][0];
+        x[e] = xv[e];
         xf[e] = (float)x[e];
         xabs += fabsf(xf[e]);
       }
@@ -1458,22 +1343,10 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
       double m1 = 0.0, m2 = -INFINITY, ctr_w = 0.0, val_w = 0.0, rat_w = 0.0;
       int w = 0;
       double bidv[PA], tvv[PA];
-#if AG_STREAM_PACK_AGENTS
-      uint32_t apk[(PA + 1) / 2];  // the slots' agents, 16 bits each (N <= 65536), for the counter pass
-#endif
 #pragma unroll
       for (int s = 0; s < P; ++s) {
-        if constexpr (AG_STREAM_SYNC == 2) {
-          if (wg_full) __syncthreads();
-        }
         const uint32_t o = s * B + i;
-        const int a = GEN ? PV[s][0] : ldg(in.part + o);
-#if AG_STREAM_PACK_AGENTS
-        if (s & 1)
-          apk[s >> 1] |= (uint32_t)a << 16;
-        else
-          apk[s >> 1] = (uint32_t)a;
-#endif
+        const int a = GEN ? pv[s] : ldg(in.part + o);
         const SlotResult q = resolve_slot<D, PRUNE, GENERAL, false, GEN, DOS>(T, K, x, xf, xabs, a, s, in, B, i,
                                                                               prm.ts_sample != 0, kTsjLoad, gk);
         if (out.item) stg(out.item + o, (int32_t)q.item);
@@ -1499,7 +1372,7 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
         }
       }
       const double price = prm.mech == AG_FIRST_PRICE ? m1 : m2;
-      const int oc = bernoulli(ctr_w, UV[0]);  // src/Auction.py:65
+      const int oc = bernoulli(ctr_w, uv);  // src/Auction.py:65
       if (out.winner) stg(out.winner + i, (int32_t)w);
       if (out.price) stg(out.price + i, charged ? price : (double)NAN);
       if (out.second_price) stg(out.second_price + i, charged ? m2 : (double)NAN);
@@ -1508,18 +1381,13 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
       if (prm.want_counters) {
 #pragma unroll
         for (int s = 0; s < P; ++s) {
-#if AG_STREAM_PACK_AGENTS
-          const int a = (int)((apk[s >> 1] >> (16 * (s & 1))) & 0xffffu);
-#else
-          const int a = GEN ? PV[s][0] : ldg(in.part + s * B + i);
-#endif
+          const int a = GEN ? pv[s] : ldg(in.part + s * B + i);
           count_post(a, charged && s == w, charged ? price : 0.0, price, m2, bidv[s], tvv[s], val_w, rat_w, oc);
         }
       }
       continue;
     }
-#if AG_EARLY_COUNT
-    if constexpr (GENERAL == kGenAll && W == 1 && P > 0) {  // A/B: +2 % on kGenTruthful (configs_1), -4 % on the mix
+    if constexpr (GENERAL == kGenAll && P > 0) {  // A/B: +2 % on kGenTruthful (configs_1), -4 % on the mix
       // each slot's outputs stored and its winner-independent counter terms added as soon
       // as it is resolved; only bid, value, true EV and est / true CTR stay live per slot
       double x[kMaxD];
@@ -1527,7 +1395,7 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
       float xabs = 1.0f;
 #pragma unroll
       for (int e = 0; e < D - 1; ++e) {
-        x[e] = XV[e][0];
+        x[e] = xv[e];
         xf[e] = (float)x[e];
         xabs += fabsf(xf[e]);
       }
@@ -1536,7 +1404,7 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
       xabs *= 1.001f;
       // compacted policy bids in the 1024-lane build (large mixed populations); A/B: the
       // 256-lane build (FP_DM_TS / FP_DR_TS, every slot a policy bidder) is 3 % faster without
-      constexpr bool kCompactPolicy = AG_POLICY_COMPACT != 0 && BT == kLargeThreads;
+      constexpr bool kCompactPolicy = BT == kLargeThreads;
       double m1 = 0.0, m2 = -INFINITY, ctr_w = 0.0;
       int w = 0;
       double bidv[PA], valv[PA], tvv[PA], ratv[PA], ctrv[PA], estv[PA], gmv[PA], prv[PA];
@@ -1547,9 +1415,9 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
 #pragma unroll
       for (int s = 0; s < P; ++s) {
         const uint32_t o = s * B + i;
-        const int a = PV[s][0];
+        const int a = pv[s];
         const SlotResult q = resolve_slot<D, PRUNE, GENERAL, kCompactPolicy, GEN, DOS>(
-            T, K, x, xf, xabs, a, s, in, B, i, prm.ts_sample != 0, AG_PREFETCH ? kTsjLoad : jv[s][0], gk);
+            T, K, x, xf, xabs, a, s, in, B, i, prm.ts_sample != 0, jv[s], gk);
         if (out.item) stg(out.item + o, (int32_t)q.item);
         if (out.est_ctr) stg(out.est_ctr + o, q.est);
         if (out.true_ctr) stg(out.true_ctr + o, q.ctr);
@@ -1587,7 +1455,7 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
             double g, pr;
             const float eps = GEN ? gen_normal1(gk.c0, gk.c1, 0, gen_stream(kDrawPolicy, s), gk.k0, gk.k1)
                                   : ldg(in.policy_eps + (size_t)s * B + i);
-            policy_bid(T.drs + PV[s][0] * T.drs_stride + 4, estv[s], valv[s], eps, T.tab, g, pr);
+            policy_bid(T.drs + pv[s] * T.drs_stride + 4, estv[s], valv[s], eps, T.tab, g, pr);
             gmv[s] = g;
             prv[s] = pr;
             bidv[s] = bidv[s] * g;
@@ -1604,7 +1472,7 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
               // eps [64] words): a wave's lanes touch consecutive words, no bank conflict
               reinterpret_cast<double *>(slots)[t] = estv[s];
               reinterpret_cast<double *>(slots)[64 + t] = valv[s];
-              reinterpret_cast<int32_t *>(slots + 1024)[t] = PV[s][0];
+              reinterpret_cast<int32_t *>(slots + 1024)[t] = pv[s];
               reinterpret_cast<float *>(slots + 1280)[t] =
                   GEN ? gen_normal1(gk.c0, gk.c1, 0, gen_stream(kDrawPolicy, s), gk.k0, gk.k1)
                       : ldg(in.policy_eps + (size_t)s * B + i);
@@ -1650,7 +1518,7 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
         if (w == s) ctr_w = ctrv[s];  // the current leader's true CTR
       }
       const double price = prm.mech == AG_FIRST_PRICE ? m1 : m2;
-      const int oc = bernoulli(ctr_w, UV[0]);  // src/Auction.py:65
+      const int oc = bernoulli(ctr_w, uv);  // src/Auction.py:65
       if (out.winner) stg(out.winner + i, (int32_t)w);
       if (out.price) stg(out.price + i, charged ? price : (double)NAN);
       if (out.second_price) stg(out.second_price + i, charged ? m2 : (double)NAN);
@@ -1659,21 +1527,19 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
       if (prm.want_counters) {
 #pragma unroll
         for (int s = 0; s < P; ++s)
-          count_post(PV[s][0], charged && s == w, charged ? price : 0.0, price, m2, bidv[s], tvv[s], valv[s],
+          count_post(pv[s], charged && s == w, charged ? price : 0.0, price, m2, bidv[s], tvv[s], valv[s],
                      ratv[s], oc);
       }
       continue;
     }
-#endif
-    Resolved<PA> r[W];
-#pragma unroll
-    for (int q = 0; q < W; ++q) {
+    Resolved<PA> r;
+    {
       double x[kMaxD];
       float xf[kMaxD];
       float xabs = 1.0f;
 #pragma unroll
       for (int e = 0; e < D - 1; ++e) {
-        x[e] = XV[e][q];
+        x[e] = xv[e];
         xf[e] = (float)x[e];
         xabs += fabsf(xf[e]);
       }
@@ -1683,72 +1549,39 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
       int ag[PA], tj[PA];
 #pragma unroll
       for (int s = 0; s < P; ++s) {
-        ag[s] = PV[s][q];
-        tj[s] = AG_PREFETCH ? kTsjLoad : jv[s][q];
+        ag[s] = pv[s];
+        tj[s] = jv[s];
       }
-      resolve<PA, D, PRUNE, GENERAL, GEN, DOS>(T, K, prm.mech, x, xf, xabs, ag, UV[q], in, B, i + q,
-                                              prm.ts_sample != 0, tj, r[q], gk);
+      resolve<PA, D, PRUNE, GENERAL, GEN, DOS>(T, K, prm.mech, x, xf, xabs, ag, uv, in, B, i, prm.ts_sample != 0, tj, r,
+                                              gk);
     }
-
-    // SoA stores, W auctions per access
 #pragma unroll
     for (int s = 0; s < P; ++s) {
       const uint32_t o = s * B + i;
-      int iv[W];
-      double bv[W], cv[W], sv[W], ev[W], gv[W], pv2[W];
-#pragma unroll
-      for (int q = 0; q < W; ++q) {
-        iv[q] = r[q].item[s];
-        bv[q] = r[q].bid[s];
-        cv[q] = r[q].ctr[s];
-        sv[q] = r[q].est[s];
-        ev[q] = r[q].bev[s];
-        gv[q] = r[q].gamma[s];
-        pv2[q] = r[q].prop[s];
-      }
-      if (out.item) st_i32<W>(out.item + o, iv);
-      if (out.bid) st_f64<W>(out.bid + o, bv);
-      if (out.est_ctr) st_f64<W>(out.est_ctr + o, sv);
-      if (out.true_ctr) st_f64<W>(out.true_ctr + o, cv);
-      if (out.best_ev) st_f64<W>(out.best_ev + o, ev);
-      if (out.gamma) st_f64<W>(out.gamma + o, gv);
-      if (out.propensity) st_f64<W>(out.propensity + o, pv2);
+      if (out.item) stg(out.item + o, (int32_t)r.item[s]);
+      if (out.bid) stg(out.bid + o, r.bid[s]);
+      if (out.est_ctr) stg(out.est_ctr + o, r.est[s]);
+      if (out.true_ctr) stg(out.true_ctr + o, r.ctr[s]);
+      if (out.best_ev) stg(out.best_ev + o, r.bev[s]);
+      if (out.gamma) stg(out.gamma + o, r.gamma[s]);
+      if (out.propensity) stg(out.propensity + o, r.prop[s]);
     }
     {
-      int wv[W], ov[W];
-      double pr[W], sp[W];
-#pragma unroll
-      for (int q = 0; q < W; ++q) {
-        wv[q] = r[q].w;
-        ov[q] = r[q].oc;
-        pr[q] = charged ? r[q].price : NAN;
-        sp[q] = charged ? r[q].second : NAN;
-      }
-      if (out.winner) st_i32<W>(out.winner + i, wv);
-      if (out.price) st_f64<W>(out.price + i, pr);
-      if (out.second_price) st_f64<W>(out.second_price + i, sp);
-      if (out.outcome) st_u8<W>(out.outcome + i, ov);
-      if (out.winner_outcome) {
-#pragma unroll
-        for (int q = 0; q < W; ++q) stg(out.winner_outcome + i + q, pack_wo(wv[q], ov[q]));
-      }
+      const double pr = charged ? r.price : NAN, sp = charged ? r.second : NAN;
+      if (out.winner) stg(out.winner + i, (int32_t)r.w);
+      if (out.price) stg(out.price + i, pr);
+      if (out.second_price) stg(out.second_price + i, sp);
+      if (out.outcome) stg(out.outcome + i, (uint8_t)r.oc);
+      if (out.winner_outcome) stg(out.winner_outcome + i, pack_wo(r.w, r.oc));
     }
-
     if (prm.want_counters) {
 #pragma unroll
-      for (int q = 0; q < W; ++q) {
-        const Resolved<PA> &rr = r[q];
-#pragma unroll
-        for (int s = 0; s < P; ++s)
-          count_slot(rr.ag[s], charged && s == rr.w, charged ? rr.price : 0.0, rr.price, rr.second, rr.bid[s],
-                     rr.ctr[s], rr.val[s], rr.est[s], rr.bev[s], rr.oc);
-      }
+      for (int s = 0; s < P; ++s)
+        count_slot(r.ag[s], charged && s == r.w, charged ? r.price : 0.0, r.price, r.second, r.bid[s], r.ctr[s],
+                   r.val[s], r.est[s], r.bev[s], r.oc);
     }
   }
 
-#undef XV
-#undef PV
-#undef UV
   if (prm.want_counters) {
     if (packed) {
       for (int a = 0; a < N; ++a) {
@@ -1836,17 +1669,18 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
 typedef void (*SimKernel)(SimParams);
 
 // Defined per participant count P in ag_sim_p.hip (one translation unit per P, compiled
-// in parallel): the k_simulate instantiation for (D, screened search, auctions per lane).
+// in parallel): the k_simulate instantiation for (D, screened search, population, lanes).
 template <int P>
-SimKernel pick_kernel_for(int D, bool prune, int W, int general, int bt);
-template <> SimKernel pick_kernel_for<0>(int, bool, int, int, int);
-template <> SimKernel pick_kernel_for<1>(int, bool, int, int, int);
-template <> SimKernel pick_kernel_for<2>(int, bool, int, int, int);
-template <> SimKernel pick_kernel_for<3>(int, bool, int, int, int);
-template <> SimKernel pick_kernel_for<4>(int, bool, int, int, int);
-template <> SimKernel pick_kernel_for<5>(int, bool, int, int, int);
-template <> SimKernel pick_kernel_for<6>(int, bool, int, int, int);
-template <> SimKernel pick_kernel_for<7>(int, bool, int, int, int);
-template <> SimKernel pick_kernel_for<8>(int, bool, int, int, int);
+SimKernel pick_kernel_for(int D, bool prune, int general, int bt);
+template <> SimKernel pick_kernel_for<0>(int, bool, int, int);
+template <> SimKernel pick_kernel_for<1>(int, bool, int, int);
+template <> SimKernel pick_kernel_for<2>(int, bool, int, int);
+template <> SimKernel pick_kernel_for<3>(int, bool, int, int);
+template <> SimKernel pick_kernel_for<4>(int, bool, int, int);
+template <> SimKernel pick_kernel_for<5>(int, bool, int, int);
+template <> SimKernel pick_kernel_for<6>(int, bool, int, int);
+template <> SimKernel pick_kernel_for<7>(int, bool, int, int);
+template <> SimKernel pick_kernel_for<8>(int, bool, int, int);
 
 }  // namespace ag
+

@@ -146,10 +146,9 @@ def _head(case, B):
 @pytest.mark.parametrize("name", ["mid", "high"])
 def test_two_auctions_per_lane(gpu, oracle, name):
     """AG_OPT_LANE_AUCTIONS = 2 on an even batch (the first 548 auctions of the rung). The shipped
-    library builds no two-auctions-per-lane kernel (AG_LANE_PAIRS 0): ag_simulate then takes the
-    one-auction build of k_simulate, so here this pins the option's even-batch dispatch (and keeps
-    an Oracle population with the option set off k_oracle); a build with AG_LANE_PAIRS=1 runs
-    k_simulate<P, 3, true, 2, kGenOracle> through the same assertions."""
+    library builds no two-auctions-per-lane kernel: ag_simulate then takes the one-auction build
+    of k_simulate, so here this pins the option's even-batch dispatch (and keeps an Oracle
+    population with the option set off k_oracle)."""
     for N, mech in ((2, 1), (4, 0)):
         case = _head(ladder_case(name, N), 548)
         orc = oracle.simulate(mech, case["items"], case["values"], case["ctx"], case["part"], case["u"])

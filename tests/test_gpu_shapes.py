@@ -180,7 +180,7 @@ def _population(pop, N):
     """Plugin kinds, shading parameters and learner states: "ts" LR-TS + TruthfulBidder (kGenTruthful);
     "all" the mix of test_general_kernel_builds_agree -- Oracle / LR-TS allocators x every bidder kind,
     learners uninitialised, bidding from fitted policies (policy_eps) and, for ValueLearningBidders,
-    by search over a host grid (kGenAll)."""
+    by search over a host grid (kGenAll); "fit" that mix without the search (no [B][P][128] grids)."""
     from auctiongym_amd import _lib
     if pop == "ts":
         return np.ones(N, np.int32), np.zeros(N, np.int32), None, None
@@ -188,7 +188,7 @@ def _population(pop, N):
     bk = np.array([(i // 2) % 5 for i in range(N)], np.int32)
     init = np.array([1 if bk[a] >= 2 and a % 3 != 1 else 0 for a in range(N)], np.int32)
     modes = np.full(N, _lib.VL_POLICY, np.int32)
-    vl = np.flatnonzero(bk == _lib.BIDDER_VALUE_LEARNING)
+    vl = np.flatnonzero(bk == _lib.BIDDER_VALUE_LEARNING) if pop == "all" else []
     for a in vl[::2]:  # every other ValueLearningBidder bids by search
         init[a], modes[a] = _lib.LEARNER_SEARCH, _lib.VL_SEARCH
     return ak, bk, init, modes
@@ -219,7 +219,8 @@ def _general_setup(seed, N, P, K, E, OE, mech, pop, sample=True, ragged=False, B
     if init is not None:
         more["gamma_raw"] = g.normal(pg[part], gs[part])
         more["policy_eps"] = g.normal(0, 1, (B, P)).astype(np.float32)
-        more["gamma_grid"] = g.uniform(0.1, 1.0, (B, P, 128))
+        if pop == "all":
+            more["gamma_grid"] = g.uniform(0.1, 1.0, (B, P, 128))
     eng = AuctionEngine(N, P, K, E, OE, mech, 1.0)
     eng.set_agent_params(ak, bk, pg, gs)
     if ragged:
@@ -330,6 +331,72 @@ def test_general_population(gpu, oracle, case):
         assert pairs == n and np.array_equal(idx.cpu().numpy(), index)
     out, cnt = _simulate(eng, inp, c["B"], _ALL_FIELDS if c["pop"] == "all" else None)
     _compare(out, cnt, orc(oracle), _case_id(c))
+    eng.close()
+
+
+# ---------------------------------------------------------------- a second grid-stride pass
+# (path, P, lanes per workgroup): one workgroup per CU and B = CUs * lanes + one full tile + 37, so
+# 255 workgroups leave k_simulate's tile loop after one tile while workgroup 0 takes a second, full
+# tile and workgroup 1 a ragged one of 37 auctions -- whose idle lanes must leave before the wave
+# barriers of the compacted fitted-policy pass -- with counters on.
+SECOND_PASS = [("deferred", 2, 256), ("early", 2, 256), ("early_compact", 2, 1024), ("streamed_ts", 3, 256),
+               ("streamed_mix", 3, 768), ("runtime_p", 9, 256), ("generate", 3, 256)]
+
+
+@pytest.mark.parametrize("path,P,lanes", SECOND_PASS, ids=[c[0] for c in SECOND_PASS])
+def test_second_grid_stride_pass(gpu, oracle, path, P, lanes):
+    """Every tile path of k_simulate over a second grid-stride pass (AG_OPT_SIM_BLOCKS_PER_CU = 1):
+    the deferred path (an Oracle population through AG_SIM_KERNEL_GENERIC), the early-count path in
+    256 lanes and in 1024 with fitted-policy bidders (the compacted pass), the streamed slots of a
+    TruthfulBidder population and of the mix's 768-lane build, and the runtime-P loop -- every output
+    and counter limb equal to the oracle's; generate mode's streamed slots against the replay of the
+    same draws on the full resident grid."""
+    import torch
+    from auctiongym_amd import _lib
+    from auctiongym_amd.engine import AuctionEngine
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    B = cus * lanes + lanes + 37
+    seed = 13000 + SECOND_PASS.index((path, P, lanes))
+    if path == "deferred":
+        g = np.random.default_rng(seed)
+        N, K, E, mech = 5, 7, 3, 0
+        items, values = _catalogue(g, N, K, E)
+        ctx, part, u = _rounds(g, N, P, E, B)
+        eng = _oracle_engine(N, P, K, E, mech, items, values)
+        eng.set_simulate_kernel(True)
+        eng.set_blocks_per_cu(1)
+        _compare(*_simulate(eng, _upload(eng, ctx, part, u), B), oracle.simulate(mech, items, values, ctx, part, u),
+                 f"second pass {path} B={B}")
+    elif path == "generate":
+        g = np.random.default_rng(seed)
+        N, K, E, OE, first = 8, 12, 5, 4, 98765432109
+        eng = AuctionEngine(N, P, K, E, OE, 1, 1.0)
+        eng.set_agent_params(np.ones(N, np.int32), np.zeros(N, np.int32))
+        eng.load_catalog(*_catalogue(g, N, K, E))
+        eng.load_lrts(g.normal(0, 1, (N, K, OE + 1)).astype(np.float32),
+                      (0.5 + 3.0 * g.random((N, K, OE + 1))).astype(np.float32), thompson_sampling=True)
+        inp = eng.alloc_inputs(B)
+        eng.generate(11, first, inp)
+        eng.generate_noise(11, first, inp)
+        out, cnt = _simulate(eng, inp, B)
+        eng.set_blocks_per_cu(1)
+        out_g, cnt_g = eng.alloc_outputs(B), eng.new_counters()
+        eng.simulate_generated(11, first, out_g, cnt_g)
+        torch.cuda.synchronize()
+        for k in out:
+            assert np.array_equal(out[k].cpu().numpy(), out_g[k].cpu().numpy(), equal_nan=True), k
+        assert torch.equal(cnt, cnt_g)
+    else:
+        # (N, K, E, OE, mech, population): the shipped shape where the build is its own (768 lanes)
+        N, K, E, OE, mech, pop = {"early": (20, 12, 5, 4, 0, "fit"), "early_compact": (20, 7, 5, 4, 1, "fit"),
+                                  "streamed_ts": (8, 12, 5, 4, 1, "ts"), "streamed_mix": (20, 7, 5, 4, 0, "fit"),
+                                  "runtime_p": (12, 3, 4, 3, 1, "fit")}[path]
+        eng, (ctx, part, u, more), orc, _ = _general_setup(seed, N, P, K, E, OE, mech, pop, B=B)
+        if lanes != 768:  # (768 lanes: the library's own choice for the mix at P >= 3)
+            eng._check(eng.L.ag_set_option(eng._h, _lib.OPT_SIM_BLOCK_THREADS, lanes), "ag_set_option")
+        eng.set_blocks_per_cu(1)
+        out, cnt = _simulate(eng, _upload(eng, ctx, part, u, **more), B, _ALL_FIELDS if pop == "fit" else None)
+        _compare(out, cnt, orc(oracle), f"second pass {path} B={B}")
     eng.close()
 
 

@@ -3,7 +3,7 @@
 bench.py (configs_2..4, bids from the constructors' policies as bench's --no-update path),
 interleaved in ONE process; outputs and counters checked equal across builds.
 
-    python tools/ab_pop.py configs_4 early [more variants...]
+    python tools/ab_pop.py configs_4 dma0 [more variants...]
     AG_AB_DENSE=1: the dense Thompson-noise layout instead of the compact one.
     AG_AB_NOCHECK=1: no output comparison (diagnostic ablation builds, make variant-p AG_ABLATE).
     A variant named "generic" is the base library with AG_SIM_KERNEL_GENERIC (k_simulate
@@ -36,7 +36,7 @@ def main():
         key, P = key.split(":")[0], int(key.split(":")[1])
     vdir = os.path.join(ROOT, "auction-gym_amd", "build", "variants")
     paths = {"base": _lib.LIB_PATH}
-    special = {"generic", "wide", "bt256", "bt1024", "nocnt", "noship", "grouporder", "packed",
+    special = {"generic", "bt256", "bt1024", "nocnt", "noship", "grouporder", "packed",
                "bpc1", "bpc2", "bpc3"}
     for n in sys.argv[2:]:  # "<variant>+generic": that build with k_simulate forced
         v = n[:-len("+generic")] if n.endswith("+generic") else n
@@ -62,9 +62,7 @@ def main():
         else:
             eng, what, B, ak, bk, st16, dims = bench.build_population(key, 0, P=P)
             eng.set_dr_state(st16, np.where(bk >= 2, 1, 0).astype(np.int32))
-        if n in ("generic", "wide"):
-            eng.set_simulate_kernel(True if n == "generic" else n)
-        elif n.endswith("+generic"):
+        if n == "generic" or n.endswith("+generic"):
             eng.set_simulate_kernel(True)
         if n == "noship":  # k_simulate's runtime-shape build
             eng._check(eng.L.ag_set_option(eng._h, _lib.OPT_SIM_SHIPPED_SHAPE, 0), "ag_set_option")

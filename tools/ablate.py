@@ -29,21 +29,21 @@ def main():
     out = eng.alloc_outputs(B, full)
     cnt = eng.new_counters()
     variants = {
-        "bench (all outputs + counters)": (False, full, True, 2),
-        "bench, 1 auction per lane": (False, full, True, 1),
-        "no counters": (False, full, False, 2),
-        "counters, winner/price only": (False, ("winner", "price"), True, 2),
-        "no outputs, no counters": (False, (), False, 2),
-        "exact item scan": (True, full, True, 1),
+        "bench (all outputs + counters)": (False, full, True, False),
+        "bench, k_simulate": (False, full, True, True),
+        "no counters": (False, full, False, False),
+        "counters, winner/price only": (False, ("winner", "price"), True, False),
+        "no outputs, no counters": (False, (), False, False),
+        "exact item scan": (True, full, True, True),
     }
     times = {k: [] for k in variants}
     st = torch.cuda.current_stream()
     for _ in range(150):  # past the clock ramp of a fresh process (tools/archive/warm_probe.py)
         eng.simulate(inp, out, cnt)
     for r in range(rounds):
-        for name, (exact, fields, want_cnt, lanes) in variants.items():
+        for name, (exact, fields, want_cnt, generic) in variants.items():
             eng.set_item_search(exact)
-            eng.set_lane_auctions(lanes)
+            eng.set_simulate_kernel(generic)  # k_simulate instead of k_oracle
             o = {k: out[k] for k in fields}
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record(st)
@@ -58,9 +58,9 @@ def main():
         print(f"{name:34s} {ms:8.4f} ms  {B / ms / 1e6:9.1f} G auctions/s  "
               f"{bpa * B / ms / 1e6:8.1f} GB/s(141B)")
     # back-to-back (sustained, as in bench.py) vs isolated launches
-    for lanes in (2, 1):
+    for generic in (False, True):
         eng.set_item_search(False)
-        eng.set_lane_auctions(lanes)
+        eng.set_simulate_kernel(generic)
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                for _ in range(20)]
         for a, b in evs:
@@ -69,7 +69,7 @@ def main():
             b.record(st)
         torch.cuda.synchronize()
         t = [a.elapsed_time(b) for a, b in evs[3:]]
-        print(f"back-to-back bench, {lanes} auct/lane     mean {np.mean(t):.4f} ms  median "
+        print(f"back-to-back bench, {'k_simulate' if generic else 'k_oracle  '}    mean {np.mean(t):.4f} ms  median "
               f"{np.median(t):.4f} ms  {bpa * B / np.mean(t) / 1e6:8.1f} GB/s")
     # pure streaming reference: read 56 B + write 85 B per auction with a copy
     src = torch.empty(B * 56 // 8, dtype=torch.float64, device="cuda")
