@@ -379,7 +379,6 @@ struct TrainLds {
   int stop;       // a NaN loss
   int exhausted;  // a noise-driven fit ran out of noise epochs before it stopped
   int flag;       // agent_allreduce_i64's broadcast
-  uint64_t gprev[2][32];  // agent_allreduce_grouped's row sums of the last two rounds
 };
 
 __device__ __forceinline__ void adam_reset(TrainLds &S) {
@@ -399,9 +398,7 @@ struct Coop {
   unsigned *bar;  // the agent's barrier lines (bar_lines)
   int ph;         // exchanges so far (identical in every workgroup of the agent)
   int64_t *acc;   // exact_totals' accumulator rows [bar_lines][32] (row 0: the totals), zero
-                  // between exchanges; AG_COOP_GROUPED: agent_allreduce_grouped's [2][groups][32]
-  unsigned *gcnt; // AG_COOP_GROUPED: its group arrival counters (group_lines, after the barrier lines)
-  unsigned rnd;   // AG_COOP_GROUPED: exact_totals calls so far
+                  // between exchanges
 };
 
 // exact totals of NV fixed-point sums over the agent's records (S.tot: hi, lo pairs), summed
@@ -416,11 +413,7 @@ template <int NV>
 __device__ __forceinline__ void exact_totals(const int64_t (&acc)[NV], TrainLds &S, Coop &C) {
   block_sums<NV>(acc, S.w, S.tot);
   if (C.nblk > 1) {
-#if AG_COOP_GROUPED
-    agcoop::agent_allreduce_grouped(C.gcnt, C.acc, 32, C.rank, C.nblk, S.tot, 2 * NV, S.tot, ++C.rnd, S.gprev);
-#else
     agcoop::agent_allreduce_i64(C.bar, C.acc, 32, C.rank, C.nblk, S.tot, 2 * NV, S.tot, &S.flag);
-#endif
     ++C.ph;
   }
 }
@@ -1134,8 +1127,7 @@ __global__ __launch_bounds__(kDrThreads, PH == 0 ? AG_DR_PH0_MIN_WAVES : AG_DR_P
   // parity buffers, then [nblk][32] accumulator rows
   int64_t *preg = partials + (size_t)(blockIdx.x - rank) * 3 * 32;
   unsigned *abar = barriers + (size_t)bar_off[a] * kBarLineWords;
-  Coop C{rank, nblk, preg, abar, 0, preg + (size_t)2 * nblk * 32, abar + (size_t)bar_lines(nblk) * kBarLineWords, 0u};
-  if (tid < 64) S.gprev[tid >> 5][tid & 31] = 0;
+  Coop C{rank, nblk, preg, abar, 0, preg + (size_t)2 * nblk * 32};
   // stage the chunk's first `cap` records in LDS (the fields this phase's fits read)
   extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
   float *lf = reinterpret_cast<float *>(s_dyn);
@@ -2119,8 +2111,7 @@ static int train_plan(ag_ctx *c, int ph, const std::vector<int64_t> &cnt, const 
     for (int a = 0; a < N; ++a)
       if (nblk[a] > 1) nblk[a] = (int32_t)(nblk[a] * f) > 1 ? (int32_t)(nblk[a] * f) : 1;
   }
-  // (an agent's lines: the tree's, then the grouped sums')
-  block_tables(P.T, [](int nb) { return bar_lines(nb) + agcoop::group_lines(nb); });
+  block_tables(P.T, [](int nb) { return bar_lines(nb); });
   int64_t most = 0;  // records of the largest workgroup chunk
   for (int a = 0; a < N; ++a) {
     P.multi |= nblk[a] > 1;

@@ -458,15 +458,12 @@ int simulate_oracle(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch_
     if ((int64_t)per_cu * cus < res) res = per_cu * cus;
   }
   // a lane resolves at most ora_lane_cap(R) auctions per launch (replica sums in range):
-  // larger batches run as consecutive launches
-  int64_t chunk_max = (int64_t)res * kThreads * ora_lane_cap(prm.L.replicas);
-#if AG_ORA_QUEUE
-  // a wave may take up to ora_lane_cap(R) auctions per lane; a launch holds half of what the
-  // grid could take (every counter has as many waves), so the rest always finds a wave
+  // larger batches run as consecutive launches. A wave may take up to ora_lane_cap(R) auctions
+  // per lane; a launch holds half of what the grid could take (every counter has as many
+  // waves), so the rest always finds a wave
   if (res >= 16) res &= ~15;
-  chunk_max = (int64_t)res * kThreads * (ora_lane_cap(prm.L.replicas) / 2);
+  int64_t chunk_max = (int64_t)res * kThreads * (ora_lane_cap(prm.L.replicas) / 2);
   prm.lane_tiles = (uint32_t)ora_lane_cap(prm.L.replicas);
-#endif
   if (chunk_max > INT32_MAX) chunk_max = INT32_MAX;
   if (c->launch_cap > 0 && c->launch_cap < chunk_max) chunk_max = c->launch_cap;
   if (chunk_max < 1) chunk_max = 1;
@@ -475,19 +472,15 @@ int simulate_oracle(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch_
     const int64_t hi = lo + chunk_max < B ? lo + chunk_max : B;
     const int64_t tiles = (hi - lo + kThreads - 1) / kThreads;
     int grid = (int)(tiles < res ? tiles : res);
-#if AG_ORA_QUEUE
     // wave w of block b serves work counter (4 b + w) mod 64, and chunk c belongs to counter
     // c mod 64: every counter the launch's chunks reach needs a wave. A grid below 16 blocks
     // (a small device or partition: res < 16) covers only 4 * grid counters -- raise it (the
     // extra blocks wait for a CU; nothing in k_oracle waits on another block)
-    const int64_t chunks = (hi - lo + 64 * AG_ORA_QUEUE_SUB - 1) / (64 * AG_ORA_QUEUE_SUB);
+    const int64_t chunks = (hi - lo + 64 * kOraChunkTiles - 1) / (64 * kOraChunkTiles);
     if (grid < 16 && chunks > 4 * (int64_t)grid) grid = (int)std::min<int64_t>(16, (chunks + 3) / 4);
-#endif
     prm.lo = (int32_t)lo;
     prm.hi = (int32_t)hi;
-#if AG_ORA_QUEUE
     AG_HIP(hipMemsetAsync(c->d_queue, 0, sizeof(uint32_t) * 64 * 32, st));
-#endif
     hipLaunchKernelGGL(k, dim3(grid), dim3(kThreads), lds, st, prm);  // generate mode: same lo/hi
     AG_HIP(hipGetLastError());
     if (counters_fx) {

@@ -23,7 +23,16 @@
 //    loser's bid is <= the price under both mechanisms) and all estimation terms;
 //  - fixed-point rounding is branch-free: the host admits a catalogue only when every value
 //    is in (0, kOraMaxValue), which bounds every term (and every replica sum) in range;
-//  - kernel arguments are only the arrays this path touches (no SGPR spills).
+//  - kernel arguments are only the arrays this path touches (no SGPR spills);
+//  - waves take 512-auction chunks from 64 work counters instead of a static grid stride: the
+//    chunks in flight stay a narrow address window however the persistent blocks drift, which
+//    is what the byte pattern's floor rewards (tools/floor: 3.64 ms persistent, 3.50 with work
+//    counters). 3.87 -> 3.73 ms per 2^27 auctions against the stride, outputs identical
+//    (profiles/r05zk_ab_wq.log); block-level claims with a barrier (4.20 ms) and per-wave
+//    64-auction claims (5.24 ms: same-address atomics serialise) lost (r05zg_ab_queue.log);
+//  - every per-slot output is stored after the slots, field by field, not as each slot
+//    resolves (3.73 -> 3.59 ms per 2^27, profiles/r05h_ab_packed.log).
+// Software-pipelined input loads lost (98 VGPRs, 4 waves, slower; HISTORY.md).
 #pragma once
 #include "ag_philox.h"
 #include "ag_sim.h"
@@ -42,27 +51,6 @@ constexpr int kOraStride = 5;      // qwords per (agent, replica): odd -> lanes 
 // sums fewer than 2^17 terms: |sum| < 2^63, no int64 overflow. Participation counts are
 // 8-bit fields in registers, flushed to LDS every kOraFlush auctions.
 constexpr double kOraMaxValue = 1024.0;
-#ifndef AG_ORA_PREFETCH
-#define AG_ORA_PREFETCH 0  // software-pipelined input loads (A/B: make variant VFLAGS=-DAG_ORA_PREFETCH=1)
-#endif
-#ifndef AG_ORA_QUEUE
-// Waves take 512-auction chunks from 64 work counters (1) instead of the static grid stride
-// (0): the chunks in flight stay a narrow address window however the persistent blocks drift,
-// which is what the byte pattern's floor rewards (tools/floor: 3.64 ms persistent, 3.50 with
-// work counters). 3.87 -> 3.73 ms per 2^27 auctions, outputs identical
-// (profiles/r05zk_ab_wq.log); block-level claims with a barrier (4.20 ms) and per-wave
-// 64-auction claims (5.24 ms: same-address atomics serialise) lost (r05zg_ab_queue.log)
-#define AG_ORA_QUEUE 1
-#endif
-#ifndef AG_ORA_QUEUE_SUB
-#define AG_ORA_QUEUE_SUB 8  // 64-auction tiles per claimed chunk (2 / 4 / 8: 3.46 / 3.41 / 3.38 ms at 5 per CU, r05zm_ab_sub_bpc.log; 8 / 16 / 32: 3.33 / 3.36 / 3.43 ms on another box, r05zn_ab_sub16.log)
-#endif
-#if AG_ORA_QUEUE && AG_ORA_PREFETCH
-#error "AG_ORA_QUEUE and AG_ORA_PREFETCH are exclusive"
-#endif
-#ifndef AG_ORA_STORE_LATE
-#define AG_ORA_STORE_LATE 1  // every per-slot output stored after the slots, field by field (A/B: 0 stores each slot's as it resolves; 3.73 -> 3.59 ms per 2^27, profiles/r05h_ab_packed.log)
-#endif
 #ifndef AG_ORA_SPECIALISE
 // k_oracle builds with the output set compile-time (FM below) for the headline's set; the host
 // picks them per call (pick_oracle_for) and runs them at kOraSpecBlocksPerCu workgroups per CU,
@@ -72,6 +60,10 @@ constexpr double kOraMaxValue = 1024.0;
 #define AG_ORA_SPECIALISE 1
 #endif
 constexpr int kOraFlush = 255;
+// 64-auction tiles per claimed chunk. Measured 2 / 4 / 8: 3.46 / 3.41 / 3.38 ms per 2^27
+// auctions at 5 workgroups per CU (profiles/r05zm_ab_sub_bpc.log); 8 / 16 / 32: 3.33 / 3.36 /
+// 3.43 ms on another machine (profiles/r05zn_ab_sub16.log)
+constexpr int kOraChunkTiles = 8;
 // default persistent grid (ag_kernels.hip simulate_oracle). Run-time form: a cap above what the
 // registers allow, so as many workgroups as fit -- 5 per CU (89 VGPRs at P = 2, D = 6). With
 // the static stride 4 streamed better than 5 (the blocks drift apart); with the work counters
@@ -132,8 +124,8 @@ struct OraParams {
   double *bid, *est_ctr, *true_ctr, *best_ev;
   uint32_t *winner_outcome;  // ABI 17: [B] winner | outcome << 31
   int64_t *partials;  // [grid][N][AG_NUM_COUNTERS][2]
-  uint32_t *queue;      // AG_ORA_QUEUE: 64 chunk counters, 32 words apart, zero at launch
-  uint32_t lane_tiles;  // AG_ORA_QUEUE: auctions one lane may take per launch
+  uint32_t *queue;      // the waves' 64 chunk counters, 32 words apart, zero at launch
+  uint32_t lane_tiles;  // auctions one lane may take per launch
   // generate mode (GEN): inputs drawn on the chip as ag_generate draws them
   uint64_t seed, first;  // Philox key; global index of auction 0 of the batch
   double scale;          // embedding_var
@@ -276,40 +268,25 @@ __global__ __launch_bounds__(kThreads) void k_oracle(OraParams prm) {
     since_flush = 0;
   };
 
-  const uint32_t stride = gridDim.x * kThreads;
-#if AG_ORA_PREFETCH
-  // the next auction's inputs are in flight while this one resolves
-  double xn[kMaxD], un = 0.0;
-  int an[P];
-  if (!GEN && lo + blockIdx.x * kThreads + tid < hi) {
-    const uint32_t i0 = lo + blockIdx.x * kThreads + tid;
-#pragma unroll
-    for (int e = 0; e < D - 1; ++e) xn[e] = ldg(prm.ctx + e * B + i0);
-#pragma unroll
-    for (int s = 0; s < P; ++s) an[s] = ldg(prm.part + s * B + i0);
-    un = ldg(prm.u + i0);
-  }
-#endif
-#if AG_ORA_QUEUE
   // wave w of block b claims from counter q = (4 b + w) mod 64; the k-th claim of counter q is
-  // the chunk 64 k + q of q_len = 64 * AG_ORA_QUEUE_SUB auctions, resolved as AG_ORA_QUEUE_SUB
+  // the chunk 64 k + q of q_len = 64 * kOraChunkTiles auctions, resolved as kOraChunkTiles
   // tiles of 64 (one auction per lane per tile). Lane 0 claims the chunk after next while the
   // current one resolves; the ticket is read only once that chunk is done. A wave makes at most
-  // lane_tiles / AG_ORA_QUEUE_SUB claims, so each lane resolves at most claims * SUB <= lane_tiles
-  // = ora_lane_cap(R) auctions: the range that keeps its exact 8-bit count fields and replica sums
-  // in range. The host sizes a launch to half of what the grid's waves may take and launches at
-  // least one wave per counter the chunks reach (simulate_oracle), so every chunk finds a wave
-  // below its cap. Tickets only grow, so a claim left in flight at the exit is past the end too.
-  (void)stride;
+  // lane_tiles / kOraChunkTiles claims, so each lane resolves at most claims * kOraChunkTiles <=
+  // lane_tiles = ora_lane_cap(R) auctions: the range that keeps its exact 8-bit count fields and
+  // replica sums in range. The host sizes a launch to half of what the grid's waves may take and
+  // launches at least one wave per counter the chunks reach (simulate_oracle), so every chunk finds
+  // a wave below its cap. Tickets only grow, so a claim left in flight at the exit is past the end
+  // too.
   const uint32_t q_lane = tid & 63;
   const uint32_t q_idx = ((uint32_t)blockIdx.x * (kThreads / 64) + (uint32_t)(tid >> 6)) & 63u;
   uint32_t *const q_ctr = prm.queue + q_idx * 32;
-  constexpr uint32_t q_len = 64 * AG_ORA_QUEUE_SUB;
+  constexpr uint32_t q_len = 64 * kOraChunkTiles;
   const uint32_t q_chunks = (hi - lo + q_len - 1) / q_len;
   uint32_t q_claims = 0;
   auto q_claim = [&]() -> uint32_t {
     uint32_t r = 0xffffffffu;
-    if (q_claims < prm.lane_tiles / AG_ORA_QUEUE_SUB) {
+    if (q_claims < prm.lane_tiles / kOraChunkTiles) {
       if (q_lane == 0) r = atomicAdd(q_ctr, 1u);
       ++q_claims;
     }
@@ -321,182 +298,149 @@ __global__ __launch_bounds__(kThreads) void k_oracle(OraParams prm) {
   };
   uint32_t q_cur = q_chunk_of(q_claim());
   uint32_t q_raw = q_claim();
-  for (;;) {
-    if (q_cur >= q_chunks) break;
+  while (q_cur < q_chunks) {
 #pragma nounroll
-    for (int q_s = 0; q_s < AG_ORA_QUEUE_SUB; ++q_s) {
-    const uint32_t i = lo + q_cur * q_len + (uint32_t)q_s * 64 + q_lane;
-    if (i >= hi) break;
-#else
-  for (uint32_t i = lo + blockIdx.x * kThreads + tid; i < hi; i += stride) {
-#endif
-    // element row + i of a stream (row: a multiple of B)
-    auto at = [&](auto *base, uint32_t row) { return base + row + i; };
-    double x[kMaxD];
-    float xf[kMaxD];
-    float xabs = 1.0f;
-    int ag[P];
-    double u;
-    if constexpr (GEN) {
-      gen_auction<P, kMaxD>((uint32_t)prm.seed, (uint32_t)(prm.seed >> 32), prm.first + i, N, P, D - 1,
-                            prm.scale, x, ag, u);
-    } else {
-#if AG_ORA_PREFETCH
+    for (int q_s = 0; q_s < kOraChunkTiles; ++q_s) {
+      const uint32_t i = lo + q_cur * q_len + (uint32_t)q_s * 64 + q_lane;
+      if (i >= hi) break;
+      // element row + i of a stream (row: a multiple of B)
+      auto at = [&](auto *base, uint32_t row) { return base + row + i; };
+      double x[kMaxD];
+      float xf[kMaxD];
+      float xabs = 1.0f;
+      int ag[P];
+      double u;
+      if constexpr (GEN) {
+        gen_auction<P, kMaxD>((uint32_t)prm.seed, (uint32_t)(prm.seed >> 32), prm.first + i, N, P, D - 1,
+                              prm.scale, x, ag, u);
+      } else {
 #pragma unroll
-      for (int e = 0; e < D - 1; ++e) x[e] = xn[e];
+        for (int e = 0; e < D - 1; ++e) x[e] = ldg(at(prm.ctx, e * B));
 #pragma unroll
-      for (int s = 0; s < P; ++s) ag[s] = an[s];
-      u = un;
-      if (i + stride < hi) {
-#pragma unroll
-        for (int e = 0; e < D - 1; ++e) xn[e] = ldg(prm.ctx + e * B + i + stride);
-#pragma unroll
-        for (int s = 0; s < P; ++s) an[s] = ldg(prm.part + s * B + i + stride);
-        un = ldg(prm.u + i + stride);
+        for (int s = 0; s < P; ++s) ag[s] = ldg(at(prm.part, s * B));
+        u = ldg(at(prm.u, 0));
       }
-#else
 #pragma unroll
-      for (int e = 0; e < D - 1; ++e) x[e] = ldg(at(prm.ctx, e * B));
-#pragma unroll
-      for (int s = 0; s < P; ++s) ag[s] = ldg(at(prm.part, s * B));
-      u = ldg(at(prm.u, 0));
-#endif
-    }
-#pragma unroll
-    for (int e = 0; e < D - 1; ++e) {
-      xf[e] = (float)x[e];
-      xabs += fabsf(xf[e]);
-    }
-    x[D - 1] = 1.0;  // intercept (src/Auction.py:33)
-    xf[D - 1] = 1.0f;
-    xabs *= 1.001f;
+      for (int e = 0; e < D - 1; ++e) {
+        xf[e] = (float)x[e];
+        xabs += fabsf(xf[e]);
+      }
+      x[D - 1] = 1.0;  // intercept (src/Auction.py:33)
+      xf[D - 1] = 1.0f;
+      xabs *= 1.001f;
 
-    int w = 0;
-    double m1 = 0.0, m2 = -INFINITY, ctr_w = 0.0, val_w = 0.0;
-    double bevs[P];
-#if AG_ORA_STORE_LATE
-    int itv[P];
-    double bdv[P], ctv[P];
-#endif
-#pragma unroll
-    for (int s = 0; s < P; ++s) {
-      const int a = ag[s];
-      const double *itm = s_items + a * L.items_stride;
-      const double *vv = s_vals + a * L.values_stride;
-      const float *row = s_scr + a * L.scr_stride;
-      const float *sv = s_scr_val + a * L.scr_val_stride;
-      uint32_t t1, t2;
-      ora_screen<D>(row, sv, L.kpairs, xf, t1, t2);
-      const bool ok = (s_amax[a] * xabs <= kPruneMaxS) && (__uint_as_float(t1 & ~15u) <= 1e30f);
-      const float thr = __uint_as_float(t1 & ~15u) * (1.0f + kPruneDelta);
-      // the f32 leader, exactly (every lane)
-      int best = (int)(t1 & 15u);
-      double c = agexp::sigmoid_fast(dot_ref<D>(itm + best * D, x), s_tab);
-      double sc = c * vv[best];
-      if (!ok || !(__uint_as_float(t2 & ~15u) > thr)) {
-        // near-tie (rare) or unscreenable lane: every item under the threshold, exactly,
-        // in increasing k (first maximum)
-        const int kf = best;
-        const double c_kf = c;
-        best = -1;
-        for (int k = 0; k < K; ++k) {
-          if (ok && k != kf && !(__uint_as_float(ora_screen_one<D>(row, sv, k, xf) & ~15u) <= thr)) continue;
-          const double ck = k == kf ? c_kf : agexp::sigmoid_fast(dot_ref<D>(itm + k * D, x), s_tab);
-          const double sk = ck * vv[k];
-          if (best < 0 || sk > sc || (sk == sc && k < best)) {
-            best = k;
-            sc = sk;
-            c = ck;
-          }
-        }
-      }
-      const double v = vv[best];
-      const double b = v * c;  // TruthfulBidder.bid: value * estimated CTR (src/Bidder.py:35)
-      bevs[s] = sc;  // max_k CTR_k * value_k (src/Auction.py:53); == b for an Oracle agent
-#if AG_ORA_STORE_LATE
-      itv[s] = best;
-      bdv[s] = b;
-      ctv[s] = c;
-#else
-      if (ora_has<FM, kOraFItem>(prm.item)) stg(at(prm.item, s * B), (int32_t)best);
-      if (ora_has<FM, kOraFBid>(prm.bid)) stg(at(prm.bid, s * B), b);
-      if (ora_has<FM, kOraFEstCtr>(prm.est_ctr)) stg(at(prm.est_ctr, s * B), c);
-      if (ora_has<FM, kOraFTrueCtr>(prm.true_ctr)) stg(at(prm.true_ctr, s * B), c);
-      if (ora_has<FM, kOraFBestEv>(prm.best_ev)) stg(at(prm.best_ev, s * B), sc);
-#endif
-      // streaming top-2, ties -> lowest slot (src/AuctionAllocation.py:19-34)
-      if (s == 0) {
-        m1 = b;
-        ctr_w = c;
-        val_w = v;
-      } else if (b > m1) {
-        m2 = m1;
-        m1 = b;
-        w = s;
-        ctr_w = c;
-        val_w = v;
-      } else if (b > m2) {
-        m2 = b;
-      }
-    }
-    const double price = fp ? m1 : m2;
-    const int oc = bernoulli(ctr_w, u);  // src/Auction.py:65 (true CTR of the winner's item)
-#if AG_ORA_STORE_LATE
-    // every per-slot output after the slots, field by field
-#pragma unroll
-    for (int s = 0; s < P; ++s)
-      if (ora_has<FM, kOraFItem>(prm.item)) stg(at(prm.item, s * B), (int32_t)itv[s]);
-#pragma unroll
-    for (int s = 0; s < P; ++s)
-      if (ora_has<FM, kOraFBid>(prm.bid)) stg(at(prm.bid, s * B), bdv[s]);
-#pragma unroll
-    for (int s = 0; s < P; ++s)
-      if (ora_has<FM, kOraFEstCtr>(prm.est_ctr)) stg(at(prm.est_ctr, s * B), ctv[s]);
-#pragma unroll
-    for (int s = 0; s < P; ++s)
-      if (ora_has<FM, kOraFTrueCtr>(prm.true_ctr)) stg(at(prm.true_ctr, s * B), ctv[s]);
-#pragma unroll
-    for (int s = 0; s < P; ++s)
-      if (ora_has<FM, kOraFBestEv>(prm.best_ev)) stg(at(prm.best_ev, s * B), bevs[s]);
-#endif
-    if (ora_has<FM, kOraFWinner>(prm.winner)) stg(at(prm.winner, 0), (int32_t)w);
-    if (ora_has<FM, kOraFPrice>(prm.price)) stg(at(prm.price, 0), charged ? price : (double)NAN);
-    if (ora_has<FM, kOraFSecondPrice>(prm.second_price)) stg(at(prm.second_price, 0), charged ? m2 : (double)NAN);
-    if (ora_has<FM, kOraFOutcome>(prm.outcome)) stg(at(prm.outcome, 0), (uint8_t)oc);
-    if (ora_has<FM, kOraFWinnerOutcome>(prm.winner_outcome)) stg(at(prm.winner_outcome, 0), pack_wo(w, oc));
-
-    if (prm.want_counters) {
+      int w = 0;
+      double m1 = 0.0, m2 = -INFINITY, ctr_w = 0.0, val_w = 0.0;
+      double bevs[P];
+      int itv[P];
+      double bdv[P], ctv[P];
 #pragma unroll
       for (int s = 0; s < P; ++s) {
-        const uint32_t addr = (uint32_t)ag[s] * agent_bytes + lane_off;
-        const bool won = charged && s == w;
-        cadd(addr, kOraSlotBestEv, ora_fx(bevs[s]));
-        if constexpr (P == 1) {  // (0 - bid) * (0 < true CTR * value), true CTR * value == bid
-          if (bevs[s] > 0.0) cadd(addr, kOraSlotUnderbid1, ora_fx(-bevs[s]));
-        }
-        if (won) {
-          cadd(addr, kOraSlotPaid, ora_fx(price));
-          if (oc) cadd(addr, kOraSlotGross, ora_fx(val_w));
-          if (fp && charged) {
-            const unsigned long long ob = ora_fx(price - m2);
-            if (ob) cadd(addr, kOraSlotOverbid, ob);
+        const int a = ag[s];
+        const double *itm = s_items + a * L.items_stride;
+        const double *vv = s_vals + a * L.values_stride;
+        const float *row = s_scr + a * L.scr_stride;
+        const float *sv = s_scr_val + a * L.scr_val_stride;
+        uint32_t t1, t2;
+        ora_screen<D>(row, sv, L.kpairs, xf, t1, t2);
+        const bool ok = (s_amax[a] * xabs <= kPruneMaxS) && (__uint_as_float(t1 & ~15u) <= 1e30f);
+        const float thr = __uint_as_float(t1 & ~15u) * (1.0f + kPruneDelta);
+        // the f32 leader, exactly (every lane)
+        int best = (int)(t1 & 15u);
+        double c = agexp::sigmoid_fast(dot_ref<D>(itm + best * D, x), s_tab);
+        double sc = c * vv[best];
+        if (!ok || !(__uint_as_float(t2 & ~15u) > thr)) {
+          // near-tie (rare) or unscreenable lane: every item under the threshold, exactly,
+          // in increasing k (first maximum)
+          const int kf = best;
+          const double c_kf = c;
+          best = -1;
+          for (int k = 0; k < K; ++k) {
+            if (ok && k != kf && !(__uint_as_float(ora_screen_one<D>(row, sv, k, xf) & ~15u) <= thr)) continue;
+            const double ck = k == kf ? c_kf : agexp::sigmoid_fast(dot_ref<D>(itm + k * D, x), s_tab);
+            const double sk = ck * vv[k];
+            if (best < 0 || sk > sc || (sk == sc && k < best)) {
+              best = k;
+              sc = sk;
+              c = ck;
+            }
           }
         }
-        if (packed) {
-          const uint64_t bit = 1ull << (8 * ag[s]);
-          n_logs_packed += bit;
-          if (won) n_won_packed += bit;
-        } else {
-          cadd(addr, kOraSlotCounts, won ? 0x100000001ull : 1ull);
+        const double v = vv[best];
+        const double b = v * c;  // TruthfulBidder.bid: value * estimated CTR (src/Bidder.py:35)
+        bevs[s] = sc;  // max_k CTR_k * value_k (src/Auction.py:53); == b for an Oracle agent
+        itv[s] = best;
+        bdv[s] = b;
+        ctv[s] = c;
+        // streaming top-2, ties -> lowest slot (src/AuctionAllocation.py:19-34)
+        if (s == 0) {
+          m1 = b;
+          ctr_w = c;
+          val_w = v;
+        } else if (b > m1) {
+          m2 = m1;
+          m1 = b;
+          w = s;
+          ctr_w = c;
+          val_w = v;
+        } else if (b > m2) {
+          m2 = b;
         }
       }
-      if (packed && ++since_flush == kOraFlush) flush_counts();
-    }
-#if AG_ORA_QUEUE
+      const double price = fp ? m1 : m2;
+      const int oc = bernoulli(ctr_w, u);  // src/Auction.py:65 (true CTR of the winner's item)
+      // every per-slot output after the slots, field by field
+#pragma unroll
+      for (int s = 0; s < P; ++s)
+        if (ora_has<FM, kOraFItem>(prm.item)) stg(at(prm.item, s * B), (int32_t)itv[s]);
+#pragma unroll
+      for (int s = 0; s < P; ++s)
+        if (ora_has<FM, kOraFBid>(prm.bid)) stg(at(prm.bid, s * B), bdv[s]);
+#pragma unroll
+      for (int s = 0; s < P; ++s)
+        if (ora_has<FM, kOraFEstCtr>(prm.est_ctr)) stg(at(prm.est_ctr, s * B), ctv[s]);
+#pragma unroll
+      for (int s = 0; s < P; ++s)
+        if (ora_has<FM, kOraFTrueCtr>(prm.true_ctr)) stg(at(prm.true_ctr, s * B), ctv[s]);
+#pragma unroll
+      for (int s = 0; s < P; ++s)
+        if (ora_has<FM, kOraFBestEv>(prm.best_ev)) stg(at(prm.best_ev, s * B), bevs[s]);
+      if (ora_has<FM, kOraFWinner>(prm.winner)) stg(at(prm.winner, 0), (int32_t)w);
+      if (ora_has<FM, kOraFPrice>(prm.price)) stg(at(prm.price, 0), charged ? price : (double)NAN);
+      if (ora_has<FM, kOraFSecondPrice>(prm.second_price)) stg(at(prm.second_price, 0), charged ? m2 : (double)NAN);
+      if (ora_has<FM, kOraFOutcome>(prm.outcome)) stg(at(prm.outcome, 0), (uint8_t)oc);
+      if (ora_has<FM, kOraFWinnerOutcome>(prm.winner_outcome)) stg(at(prm.winner_outcome, 0), pack_wo(w, oc));
+
+      if (prm.want_counters) {
+#pragma unroll
+        for (int s = 0; s < P; ++s) {
+          const uint32_t addr = (uint32_t)ag[s] * agent_bytes + lane_off;
+          const bool won = charged && s == w;
+          cadd(addr, kOraSlotBestEv, ora_fx(bevs[s]));
+          if constexpr (P == 1) {  // (0 - bid) * (0 < true CTR * value), true CTR * value == bid
+            if (bevs[s] > 0.0) cadd(addr, kOraSlotUnderbid1, ora_fx(-bevs[s]));
+          }
+          if (won) {
+            cadd(addr, kOraSlotPaid, ora_fx(price));
+            if (oc) cadd(addr, kOraSlotGross, ora_fx(val_w));
+            if (fp && charged) {
+              const unsigned long long ob = ora_fx(price - m2);
+              if (ob) cadd(addr, kOraSlotOverbid, ob);
+            }
+          }
+          if (packed) {
+            const uint64_t bit = 1ull << (8 * ag[s]);
+            n_logs_packed += bit;
+            if (won) n_won_packed += bit;
+          } else {
+            cadd(addr, kOraSlotCounts, won ? 0x100000001ull : 1ull);
+          }
+        }
+        if (packed && ++since_flush == kOraFlush) flush_counts();
+      }
     }
     q_cur = q_chunk_of(q_raw);
     q_raw = q_claim();
-#endif
   }
 
   if (!prm.want_counters) return;

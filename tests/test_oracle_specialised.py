@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 FULL = ("winner", "price", "second_price", "outcome", "item", "bid", "est_ctr", "true_ctr", "best_ev")
 PER_SLOT = ("item", "bid", "est_ctr", "true_ctr", "best_ev")
 PER_AUCTION = ("winner", "price", "second_price", "outcome")
-# a lone lane; the tile edge (64); the chunk edge (64 * AG_ORA_QUEUE_SUB = 512); the wrap where
+# a lone lane; the tile edge (64); the chunk edge (64 * kOraChunkTiles = 512); the wrap where
 # work counter 0 is claimed a second time (64 counters * 512 = 32768)
 SIZES = (1, 63, 64, 65, 511, 512, 513, 32767, 32768, 32769)
 FIRST_PRICE, SECOND_PRICE = 0, 1
