@@ -774,6 +774,14 @@ int ag_lrts_update(ag_ctx *c, const ag_lrts_samples *s, int32_t *epochs, float *
         nblk[a] = (int32_t)(nblk[a] * f) > 1 ? (int32_t)(nblk[a] * f) : 1;
         want += nblk[a];
       }
+    // the floor stops at 1, so many agents of one workgroup can keep the total above the
+    // resident grid: then every agent trains on one workgroup (a plain launch of any size;
+    // the stream loop takes any n)
+    if (want > w.coop_blocks) {
+      for (int a = 0; a < N; ++a)
+        if (nblk[a] > 1) nblk[a] = 1;
+      want = agents;
+    }
   }
   int64_t pwords = 0;
   int lines = 0;

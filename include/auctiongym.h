@@ -457,7 +457,26 @@ int ag_lrts_collect(ag_ctx *ctx, int64_t B, const ag_batch_in *in, const ag_batc
  * next ag_simulate. Synchronises `stream` (reads the sample count). epochs: host [N]
  * epochs run per agent (0: not trained), may be NULL; loss_trace: dev float32
  * [N][AG_LRTS_MAX_EPOCHS] per-epoch loss.item(), may be NULL. Arithmetic:
- * oracle/ag_oracle.c ora_lrts_update. */
+ * oracle/ag_oracle.c ora_lrts_update.
+ * Range of the exact sums. A lane adds its samples' terms in one int64 per (item, column)
+ * before they are split into halves that cannot overflow: gradient terms rint((p - y) x 2^40)
+ * with |p - y| <= 1, Laplace terms rint(w x^2 2^40) with w = P (1 - P) <= 1/4. The sums equal
+ * the oracle's (and do not depend on where a sample lands) while, for every item and column,
+ * the samples ONE LANE holds keep
+ *     sum |x| <= 2^22   and   sum x^2 <= 2^24        (so every |x| <= 2^22: a single rint
+ * argument stays below 2^63), and the agent's samples over all lanes keep sum |x| <= 2^46
+ * and sum x^2 <= 2^48 (the sums of the gradient and the Laplace high halves). Each bound
+ * carries a factor of two of margin: the code wraps at sum |x| = 2^23 and sum x^2 = 2^25 per
+ * lane (2^47 and 2^49 per agent); the margin covers the terms' rounding and the float32
+ * rounding of x^2. Outside that a lane's sum wraps and the total read back is a
+ * different number, silently. A lane holds every 256th sample of its workgroup's chunk: at
+ * most 16 samples at the default split, at most ceil(n / 256) of an agent's n samples when
+ * the agent trains on one workgroup (a grid shared out among many agents). Contexts of
+ * magnitude X with S samples per lane are inside while S X <= 2^22 and S X^2 <= 2^24:
+ * |x| <= 8 allows 2^18 samples per lane, 2^26 per agent, so no population the simulator
+ * produces leaves the range and nothing is refused; a caller scaling contexts by 2^10 or
+ * more must check it. The same holds for ag_lrts_rp_* (at most 8 samples per lane and
+ * launch). The BCE terms (<= 100 * 2^32 each) cannot wrap below 2^24 samples per lane. */
 int ag_lrts_update(ag_ctx *ctx, const ag_lrts_samples *samples, int32_t *epochs,
                    float *loss_trace, void *stream);
 
