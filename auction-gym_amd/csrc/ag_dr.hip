@@ -1741,13 +1741,15 @@ __global__ __launch_bounds__(kDrThreads) void k_sh_gather(ag_shading_samples s, 
   }
 }
 
-int grid_over(int64_t n) {
-  int64_t g = (n + kDrThreads - 1) / kDrThreads;
-  if (g > 4096) g = 4096;
-  return (int)(g < 1 ? 1 : g);
-}
+int grid_over(int64_t n) { return agtrain::grid_over(n, kDrThreads); }
+
+DrRecords records_of(const agtrain::SortedRecs &S) { return DrRecords{S.ctr, S.val, S.gam, S.prop, S.util, S.won}; }
 
 }  // namespace
+
+using agtrain::BlockTables;
+using agtrain::Carve;
+using agtrain::SortedRecs;
 
 void ag_dr_release(ag_ctx *c) {
   ag_dr_ws &w = c->dr;
@@ -1765,15 +1767,6 @@ void ag_dr_release(ag_ctx *c) {
   (void)hipFree(w.rp.pipe);
   (void)hipFree(w.rp.pipe_st);
   w = ag_dr_ws();
-}
-
-// The sorted record arrays of the workspace (sort_records' layout) for n records
-static DrRecords sorted_view(ag_dr_ws &w, int64_t n, double **eu) {
-  const int64_t cap = n > 0 ? n : 1;
-  double *b = (double *)w.buf;
-  *eu = b + 5 * cap;
-  return DrRecords{b, b + cap, b + 2 * cap, b + 3 * cap, b + 4 * cap,
-                   (const uint8_t *)((uint32_t *)((uint64_t *)(b + 6 * cap) + 2 * cap) + 2 * cap)};
 }
 
 // k_bidder_pipe's record-cache budgets (dynamic LDS per workgroup: 4 / 3 per CU) and the
@@ -1807,28 +1800,17 @@ static int pipe_run(ag_ctx *c, const std::vector<int32_t> &slots, const std::vec
   for (int ph = 0; ph < 2; ++ph)
     if (!rp.pipe_blocks[ph]) {
       const void *fn = ph == 0 ? (const void *)k_bidder_pipe<0> : (const void *)k_bidder_pipe<1>;
-      int per_cu = 0, cus = 0;
       AG_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPipeLds[ph]));
-      AG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kDrThreads, kPipeLds[ph]));
-      AG_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-      rp.pipe_blocks[ph] = std::max(1, per_cu * cus);
+      AG_HIP(agtrain::resident_blocks(fn, kDrThreads, kPipeLds[ph], c->device, &rp.pipe_blocks[ph]));
     }
-  // device tables, sized once for the largest grid: [3][kPipeMaxAgents] i32 per phase, then
-  // per phase the acc rows [kPipeMaxAgents][lines][32] i64 and barrier lines (the two
-  // launches of a run never share a word)
+  // device tables, sized once for the largest grid (every slot's rows [lines][32]), 64 bytes
+  // between the phases'
   const size_t lines_max = (size_t)std::max(1, bar_lines(std::max(rp.pipe_blocks[0], rp.pipe_blocks[1]), kPipeFanIn));
-  const size_t rows_max = (size_t)kPipeMaxAgents * lines_max * 32;
-  const size_t per_ph = 3 * kPipeMaxAgents * sizeof(int32_t) + rows_max * (sizeof(int64_t) + sizeof(unsigned)) + 64;
-  if (2 * per_ph > rp.pipe_bytes) {
-    (void)hipFree(rp.pipe);  // (synchronises: no launch of an earlier run uses it any more)
-    rp.pipe = nullptr;
-    rp.pipe_bytes = 0;
-    AG_HIP(hipMalloc(&rp.pipe, 2 * per_ph));
-    rp.pipe_bytes = 2 * per_ph;
-  }
+  const size_t per_ph = agtrain::layout_bytes(agtrain::pipe_layout, kPipeMaxAgents, kPipeMaxAgents * lines_max * 32) + 64;
+  AG_HIP(agtrain::dev_reserve(&rp.pipe, &rp.pipe_bytes, 2 * per_ph));
   for (int ph = 0; ph < 2; ++ph) {
     if (!(phases >> ph & 1)) continue;
-    const void *fn = ph == 0 ? (const void *)k_bidder_pipe<0> : (const void *)k_bidder_pipe<1>;
+    const auto fn = ph == 0 ? k_bidder_pipe<0> : k_bidder_pipe<1>;
     const int G = (int)std::max<int64_t>(1, std::min<int64_t>(rp.pipe_blocks[ph], (recs + want_recs - 1) / want_recs));
     const int lines = std::max(1, bar_lines(G, kPipeFanIn));
     // record caches after the FitSt copies: slot i caches min(chunk, share) records
@@ -1854,15 +1836,14 @@ static int pipe_run(ag_ctx *c, const std::vector<int32_t> &slots, const std::vec
     }
     if (off > kPipeLds[ph])
       return ag_set_error(AG_ERR_UNSUPPORTED, "k_bidder_pipe: record cache plan %zu > %zu", off, kPipeLds[ph]);
-    int32_t *d_tab = (int32_t *)((char *)rp.pipe + ph * per_ph);
-    int64_t *d_acc = (int64_t *)(((uintptr_t)(d_tab + 3 * kPipeMaxAgents) + 15) & ~(uintptr_t)15);
     const size_t rows = (size_t)NA * lines * 32;
-    unsigned *d_bar = (unsigned *)(d_acc + rows);
-    AG_HIP(hipMemcpyAsync(d_tab, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, st));
-    AG_HIP(hipMemsetAsync(d_acc, 0, rows * (sizeof(int64_t) + sizeof(unsigned)), st));
+    Carve carve((char *)rp.pipe + ph * per_ph);
+    const agtrain::PipeTables D = agtrain::pipe_layout(carve, kPipeMaxAgents, rows);
+    AG_HIP(hipMemcpyAsync(D.tab, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, st));
+    AG_HIP(hipMemsetAsync(D.acc, 0, rows * (sizeof(int64_t) + sizeof(unsigned)), st));
     PipeArgs A;
     A.NA = NA;
-    A.agents = d_tab;
+    A.agents = D.tab;
     A.bkind = c->d_bkind;
     A.bmode = w.mode;
     A.initialised = w.init;
@@ -1872,11 +1853,11 @@ static int pipe_run(ag_ctx *c, const std::vector<int32_t> &slots, const std::vec
     A.eu_ws = eu;
     A.st = d_st;
     A.tot_in = tot_in;
-    A.acc = d_acc;
-    A.bars = d_bar;
+    A.acc = D.acc;
+    A.bars = D.bar;
     A.lines = lines;
-    A.lds_off = d_tab + kPipeMaxAgents;
-    A.lds_cap = d_tab + 2 * kPipeMaxAgents;
+    A.lds_off = D.tab + kPipeMaxAgents;
+    A.lds_cap = D.tab + 2 * kPipeMaxAgents;
     A.noise = nz.noise;
     A.noise_off = nz.noise_off;
     A.noise_stride = nz.stride;
@@ -1888,8 +1869,7 @@ static int pipe_run(ag_ctx *c, const std::vector<int32_t> &slots, const std::vec
     A.prof = nullptr;
     const bool prof = getenv("AG_PIPE_PROF") != nullptr;
     if (prof) AG_HIP(hipMalloc(&A.prof, sizeof(long long) * 8 * G));
-    void *args[] = {&A};
-    AG_HIP(hipLaunchCooperativeKernel(fn, dim3(G), dim3(kDrThreads), args, kPipeLds[ph], st));
+    AG_HIP(agtrain::launch_group(fn, true, G, kDrThreads, kPipeLds[ph], st, A));
     if (prof) {  // diagnostics: mean over workgroups of each part, microseconds (100 MHz clock)
       std::vector<long long> h(8 * (size_t)G);
       AG_HIP(hipMemcpy(h.data(), A.prof, sizeof(long long) * 8 * G, hipMemcpyDeviceToHost));
@@ -1925,19 +1905,50 @@ static void learner_flags(ag_ctx *c, const int32_t *init) {
   }
 }
 
+// The host's end of learner a's fit. f: its FitSt (k_bidder_pipe, the per-epoch launches), whose
+// epochs and status go out and whose models go into the agent's `state` row unless the
+// ValueLearningBidder's no-win fallback trained nothing (status 1, src/Bidder.py:206-211); null
+// after k_bidder_train, which wrote all three itself. A fit that waits for noise epochs past the
+// caller's (status -3) is not applied. Otherwise the agent bids from what it fitted from now on
+// (src/Bidder.py:321, :430, :612-613): the policy, the win-rate search (ValueLearningBidder
+// 'search'), or the Gaussian again after the fallback. Returns rc or, the first time, the
+// reference's error for an update without logs (-1) or a NaN loss (-2).
+static int apply_fit(const ag_ctx *c, int a, const FitSt *f, int mode, float *state, int32_t *init, int32_t *ep,
+                     int32_t *status, int rc) {
+  static const char *names[] = {"", "", "ValueLearningBidder", "PolicyLearningBidder", "DoublyRobustBidder"};
+  const int bk = c->h_bkind[a];
+  if (f) {
+    for (int j = 0; j < 3; ++j) ep[j] = f->ep[j];
+    *status = f->status;
+    if (f->fit != kFitDone) {
+      *status = -3;
+      ep[2] = f->epoch;
+    } else if (f->status != 1) {
+      for (int j = 0; j < 4; ++j) state[j] = f->wr[j];
+      for (int j = 0; j < 12; ++j) state[4 + j] = f->pol[j];
+    }
+  }
+  if (*status == -3) return rc;
+  if (*status == -1 && rc == AG_OK)
+    rc = ag_set_error(AG_ERR_INVALID, "agent %d: %s.update without logs", a, names[bk]);
+  if (*status == -2 && rc == AG_OK)
+    rc = ag_set_error(AG_ERR_INVALID, "agent %d: %s: NAN DETECTED! in losses (src/Bidder.py:%d)", a, names[bk],
+                      bk == AG_BIDDER_DOUBLY_ROBUST ? 592 : 409);
+  if (bk == AG_BIDDER_VALUE_LEARNING)
+    *init = *status == 1 ? AG_LEARNER_UNINITIALISED : (mode == AG_VL_POLICY ? AG_LEARNER_POLICY : AG_LEARNER_SEARCH);
+  else
+    *init = AG_LEARNER_POLICY;
+  return rc;
+}
+
 // workspace: counts / offsets / cursors, the Adam bias-correction table, the learner state
 static int dr_ws_ready(ag_ctx *c) {
   ag_dr_ws &w = c->dr;
   if (w.adam_tab) return AG_OK;
   const int N = c->shape.num_agents;
-  double *tab = new double[2 * kDrEpochs];
-  for (int t = 0; t < kDrEpochs; ++t) {  // torch.optim.Adam: Python floats, libm pow
-    tab[t] = 1.0 - pow(0.9, (double)(t + 1));
-    tab[kDrEpochs + t] = pow(1.0 - pow(0.999, (double)(t + 1)), 0.5);
-  }
-  hipError_t e = hipMalloc(&w.adam_tab, sizeof(double) * 2 * kDrEpochs);
-  if (e == hipSuccess) e = hipMemcpy(w.adam_tab, tab, sizeof(double) * 2 * kDrEpochs, hipMemcpyHostToDevice);
-  delete[] tab;
+  const std::vector<double> tab = agtrain::adam_bias_table(kDrEpochs);
+  hipError_t e = hipMalloc(&w.adam_tab, sizeof(double) * tab.size());
+  if (e == hipSuccess) e = hipMemcpy(w.adam_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc(&w.counts, sizeof(int64_t) * (3 * (size_t)N + 1));
   if (e == hipSuccess) e = hipMalloc(&w.state, sizeof(float) * 16 * (size_t)N);
   if (e == hipSuccess) e = hipMemset(w.state, 0, sizeof(float) * 16 * (size_t)N);
@@ -1960,14 +1971,7 @@ static int dr_ws_ready(ag_ctx *c) {
 
 // The learning bidders' records of a store sorted into (agent, log order) in the workspace
 // (stable radix sorts on the 64-bit order, then on agent; every field gathered): cnt / off host
-// [N] / [N + 1];
-// SortedRecs: device arrays [n] (eu: the estimated-utility workspace) and d_off [N + 1].
-struct SortedRecs {
-  double *ctr, *val, *gam, *prop, *util, *eu;
-  uint8_t *won;
-  int64_t *d_off;
-  int64_t n;
-};
+// [N] / [N + 1]; out: device arrays [n] and d_off [N + 1].
 static int sort_records(ag_ctx *c, const ag_shading_samples *s, std::vector<int64_t> &cnt, std::vector<int64_t> &off,
                         SortedRecs &out, hipStream_t st) {
   const int N = c->shape.num_agents;
@@ -1990,22 +1994,16 @@ static int sort_records(ag_ctx *c, const ag_shading_samples *s, std::vector<int6
                                             (uint32_t *)nullptr, (uint32_t *)nullptr, (int)(n > 0 ? n : 1), 0, 32,
                                             st));
   if (agent_tmp > sort_tmp) sort_tmp = agent_tmp;
-  const size_t rec_bytes = (size_t)6 * sizeof(double) + 1;
-  const size_t need = (size_t)(n > 0 ? n : 1) * (rec_bytes + 24) + sort_tmp + 256;
-  if (need > w.buf_bytes) {
-    (void)hipFree(w.buf);
-    w.buf = nullptr;
-    const size_t bytes = need + (need >> 2);
-    AG_HIP(hipMalloc(&w.buf, bytes));
-    w.buf_bytes = bytes;
-  }
   const size_t cap = (size_t)(n > 0 ? n : 1);
-  double *b_ctr = (double *)w.buf, *b_val = b_ctr + cap, *b_gam = b_val + cap, *b_prop = b_gam + cap,
-         *b_util = b_prop + cap, *b_eu = b_util + cap;
-  uint64_t *k_in = (uint64_t *)(b_eu + cap), *k_out = k_in + cap;
-  uint32_t *i_in = (uint32_t *)(k_out + cap), *i_out = i_in + cap;
-  uint8_t *b_won = (uint8_t *)(i_out + cap);
-  void *tmp = (void *)(((uintptr_t)(b_won + cap) + 255) & ~(uintptr_t)255);
+  const size_t need = agtrain::layout_bytes(agtrain::sorted_layout, cap, sort_tmp);
+  AG_HIP(agtrain::dev_reserve(&w.buf, &w.buf_bytes, need, need + (need >> 2)));
+  Carve carve(w.buf);
+  out = agtrain::sorted_layout(carve, cap, sort_tmp);
+  out.d_off = d_off;
+  out.n = n;
+  uint64_t *k_in = out.k_in, *k_out = out.k_out;
+  uint32_t *i_in = out.i_in, *i_out = out.i_out;
+  void *tmp = out.tmp;
   if (n > 0) {
     if (!s->order) return ag_set_error(AG_ERR_INVALID, "learning bidders' update: the store needs order");
     hipLaunchKernelGGL(k_sh_keys, dim3(grid_over(n)), dim3(kDrThreads), 0, st, *s, n, k_in, i_in);
@@ -2018,37 +2016,11 @@ static int sort_records(ag_ctx *c, const ag_shading_samples *s, std::vector<int6
     int agent_bits = 1;
     while ((1ll << agent_bits) < N) ++agent_bits;
     AG_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, agent_tmp, a_in, a_out, i_out, i_in, (int)n, 0, agent_bits, st));
-    hipLaunchKernelGGL(k_sh_gather, dim3(grid_over(n)), dim3(kDrThreads), 0, st, *s, n, i_in, b_ctr, b_val, b_gam,
-                       b_prop, b_util, b_won);
+    hipLaunchKernelGGL(k_sh_gather, dim3(grid_over(n)), dim3(kDrThreads), 0, st, *s, n, i_in, out.ctr, out.val,
+                       out.gam, out.prop, out.util, out.won);
     AG_HIP(hipGetLastError());
   }
-  out = SortedRecs{b_ctr, b_val, b_gam, b_prop, b_util, b_eu, b_won, d_off, n};
   return AG_OK;
-}
-
-// The block tables of a launch, from the workgroups per agent (nblk; 0: the agent is not in the
-// launch): workgroup b works on agent blk_agent[b] as its workgroup blk_rank[b] (an agent's
-// workgroups have consecutive indices); agent a's barrier lines (and accumulator rows) start
-// at line bar_off[a], lines_of(nblk[a]) of them, `lines` in all.
-struct BlockTables {
-  std::vector<int32_t> nblk, blk_agent, blk_rank, bar_off;
-  int lines = 0;
-};
-static void block_tables(BlockTables &T, int (*lines_of)(int nblk)) {
-  const int N = (int)T.nblk.size();
-  T.bar_off.assign(N, 0);
-  T.blk_agent.clear();
-  T.blk_rank.clear();
-  T.lines = 0;
-  for (int a = 0; a < N; ++a) {
-    if (!T.nblk[a]) continue;
-    T.bar_off[a] = T.lines;
-    T.lines += lines_of(T.nblk[a]);
-    for (int r = 0; r < T.nblk[a]; ++r) {
-      T.blk_agent.push_back(a);
-      T.blk_rank.push_back(r);
-    }
-  }
 }
 
 // One phase's launch of k_bidder_train (ag_bidder_update) for the learners `trained`: the
@@ -2061,10 +2033,9 @@ static void block_tables(BlockTables &T, int (*lines_of)(int nblk)) {
 // keeps one workgroup per kBidderChunk records. Both phases use the same rule with their
 // own grid.
 struct TrainPlan {
-  const void *fn = nullptr;
+  decltype(&k_bidder_train<0>) fn = nullptr;
   BlockTables T;
-  int G = 0, nf = 0;
-  bool multi = false;
+  int nf = 0;
   int64_t rcap = 0;
   size_t dyn = 0;
 };
@@ -2072,18 +2043,13 @@ static int train_plan(ag_ctx *c, int ph, const std::vector<int64_t> &cnt, const 
                       TrainPlan &P) {
   ag_dr_ws &w = c->dr;
   const int N = c->shape.num_agents;
-  P.fn = ph == 0 ? (const void *)k_bidder_train<0> : (const void *)k_bidder_train<1>;
+  P.fn = ph == 0 ? k_bidder_train<0> : k_bidder_train<1>;
   const size_t lds_budget = ph == 0 ? kRecLdsBytes0 : kRecLdsBytes;
   int &coop_blocks = ph == 0 ? w.coop_blocks0 : w.coop_blocks;
-  if (!coop_blocks) {
-    int per_cu = 0, cus = 0;
-    AG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, P.fn, kDrThreads, lds_budget));
-    AG_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-    coop_blocks = per_cu * cus > 0 ? per_cu * cus : 1;
-  }
+  AG_HIP(agtrain::resident_blocks((const void *)P.fn, kDrThreads, lds_budget, c->device, &coop_blocks));
   std::vector<int32_t> &nblk = P.T.nblk;
   nblk.assign(N, 0);
-  int64_t want = 0, exact_recs = 0, fixed_blocks = 0;
+  int64_t exact_recs = 0, fixed_blocks = 0;
   int nf = 0;  // float fields of the record cache: 3 (win-rate, ValueLearning), 5 (PolicyLearning), 6 (DR)
   for (int a = 0; a < N; ++a) {
     const int bk = c->h_bkind[a];
@@ -2098,29 +2064,17 @@ static int train_plan(ag_ctx *c, int ph, const std::vector<int64_t> &cnt, const 
       nblk[a] = -1;
     }
   }
-  for (int a = 0; a < N; ++a) {
+  for (int a = 0; a < N; ++a)
     if (nblk[a] < 0) {
       const int64_t avail = std::max<int64_t>(1, coop_blocks - fixed_blocks);
       const int64_t share = exact_recs > 0 ? (int64_t)((double)avail * (double)cnt[a] / (double)exact_recs) : 1;
       nblk[a] = (int32_t)std::max<int64_t>(1, std::min<int64_t>((cnt[a] + kMinChunk - 1) / kMinChunk, share));
     }
-    want += nblk[a];
-  }
-  if (want > coop_blocks) {  // share the resident grid out
-    const double f = (double)coop_blocks / (double)want;
-    for (int a = 0; a < N; ++a)
-      if (nblk[a] > 1) nblk[a] = (int32_t)(nblk[a] * f) > 1 ? (int32_t)(nblk[a] * f) : 1;
-  }
-  block_tables(P.T, [](int nb) { return bar_lines(nb); });
+  agtrain::share_out(nblk, coop_blocks);
+  agtrain::block_tables(P.T, [](int nb) { return bar_lines(nb); });
   int64_t most = 0;  // records of the largest workgroup chunk
-  for (int a = 0; a < N; ++a) {
-    P.multi |= nblk[a] > 1;
+  for (int a = 0; a < N; ++a)
     if (nblk[a]) most = std::max<int64_t>(most, (cnt[a] + nblk[a] - 1) / nblk[a]);
-  }
-  P.G = (int)P.T.blk_agent.size();
-  if (P.multi && P.G > coop_blocks)
-    return ag_set_error(AG_ERR_UNSUPPORTED, "ag_bidder_update: %d learning bidders need more co-resident "
-                        "workgroups (%d) than the device holds (%d)", N, P.G, coop_blocks);
   // record cache: [nf][cap] floats + [cap] bytes, cap a multiple of the block size
   const int64_t rcap_fit = nf ? (int64_t)lds_budget / (4 * nf + 1) / kDrThreads * kDrThreads : 0;
   P.rcap = std::min<int64_t>(rcap_fit, (most + kDrThreads - 1) / kDrThreads * kDrThreads);
@@ -2130,47 +2084,23 @@ static int train_plan(ag_ctx *c, int ph, const std::vector<int64_t> &cnt, const 
   return AG_OK;
 }
 
-// ag_bidder_update's device tables (one buffer, shared by its two launches) and outputs
-struct TrainDev {
-  int64_t *part;
-  unsigned *bar;
-  int32_t *bagent, *brank, *nblk, *baroff;
-  float *wr;
-  int64_t *noff;
-  int32_t *epochs, *stat;
-};
-static int train_launch(ag_ctx *c, const TrainPlan &P, const TrainDev &D, const SortedRecs &SR, const float *noise,
-                        int32_t noise_epochs, float *traces, hipStream_t st) {
-  if (P.G == 0) return AG_OK;
+// One launch of a plan: its tables into D (ag_bidder_update's, shared by the two launches)
+static int train_launch(ag_ctx *c, const TrainPlan &P, const agtrain::TrainTables &D, const SortedRecs &SR,
+                        const float *noise, const int64_t *d_noff, int32_t noise_epochs, int32_t *d_epochs,
+                        int32_t *d_stat, float *traces, hipStream_t st) {
+  const int G = P.T.G(), N = c->shape.num_agents;
+  if (G == 0) return AG_OK;
   ag_dr_ws &w = c->dr;
-  const int N = c->shape.num_agents;
-  AG_HIP(hipMemcpyAsync(D.bagent, P.T.blk_agent.data(), sizeof(int32_t) * P.G, hipMemcpyHostToDevice, st));
-  AG_HIP(hipMemcpyAsync(D.brank, P.T.blk_rank.data(), sizeof(int32_t) * P.G, hipMemcpyHostToDevice, st));
+  AG_HIP(hipMemcpyAsync(D.bagent, P.T.blk_agent.data(), sizeof(int32_t) * G, hipMemcpyHostToDevice, st));
+  AG_HIP(hipMemcpyAsync(D.brank, P.T.blk_rank.data(), sizeof(int32_t) * G, hipMemcpyHostToDevice, st));
   AG_HIP(hipMemcpyAsync(D.nblk, P.T.nblk.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
   AG_HIP(hipMemcpyAsync(D.baroff, P.T.bar_off.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
   if (P.T.lines) AG_HIP(hipMemsetAsync(D.bar, 0, sizeof(unsigned) * kBarLineWords * P.T.lines, st));
-  if (P.multi) AG_HIP(hipMemsetAsync(D.part, 0, sizeof(int64_t) * 96 * (size_t)P.G, st));  // accumulators
-  DrRecords R{SR.ctr, SR.val, SR.gam, SR.prop, SR.util, SR.won};
-  const int32_t *cbk = c->d_bkind, *cmode = w.mode, *cinit = w.init, *cbo = D.baroff;
-  const int32_t *cbagent = D.bagent, *cbrank = D.brank, *cnblk = D.nblk;
-  const int64_t *coff = SR.d_off, *cnoff = D.noff;
-  double *ceu = SR.eu;
-  float *cstate = w.state, *ctr = traces, *cwr = D.wr;
-  int32_t *cep = D.epochs, *cstat = D.stat;
-  int64_t *cpart = D.part;
-  unsigned *cbar = D.bar;
-  int cne = noise_epochs;
-  uint64_t cseed = c->fit_noise_seed;
-  const double *ctab = w.adam_tab;
-  int cnf = P.nf;
-  int64_t ccap = P.rcap;
-  void *args[] = {&cbk,    &cmode, &cbagent, &cbrank, &cnblk, &coff, &R,     &ceu,
-                  &cstate, &cwr,   &cinit,   &noise,  &cnoff, &cne,  &cseed, &ctab,
-                  &cep,    &cstat, &ctr,     &cpart,  &cbar,  &cbo,  &cnf,   &ccap};
-  if (P.multi)  // workgroups of one agent wait for each other: they must all be resident
-    AG_HIP(hipLaunchCooperativeKernel(P.fn, dim3(P.G), dim3(kDrThreads), args, P.dyn, st));
-  else
-    AG_HIP(hipLaunchKernel(P.fn, dim3(P.G), dim3(kDrThreads), args, P.dyn, st));
+  if (P.T.multi()) AG_HIP(hipMemsetAsync(D.part, 0, sizeof(int64_t) * 96 * (size_t)G, st));  // accumulators
+  AG_HIP(agtrain::launch_group(P.fn, P.T.multi(), G, kDrThreads, P.dyn, st, c->d_bkind, w.mode, D.bagent, D.brank,
+                               D.nblk, SR.d_off, records_of(SR), SR.eu, w.state, D.wr, w.init, noise, d_noff,
+                               noise_epochs, c->fit_noise_seed, w.adam_tab, d_epochs, d_stat, traces, D.part, D.bar,
+                               D.baroff, P.nf, P.rcap));
   return AG_OK;
 }
 
@@ -2207,11 +2137,7 @@ int ag_shading_counts(ag_ctx *c, const ag_shading_samples *s, int64_t *counts, v
   const int N = c->shape.num_agents;
   hipStream_t st = (hipStream_t)stream;
   uint64_t n = 0;
-  AG_HIP(hipMemcpyAsync(&n, s->count, sizeof n, hipMemcpyDeviceToHost, st));
-  AG_HIP(hipStreamSynchronize(st));
-  if ((int64_t)n > s->capacity)
-    return ag_set_error(AG_ERR_INVALID, "ag_shading_counts: %llu records overflowed the store (capacity %lld)",
-                        (unsigned long long)n, (long long)s->capacity);
+  if (int rc = agtrain::read_store_count(s->count, s->capacity, "ag_shading_counts", "records", st, &n)) return rc;
   int64_t *d_counts = c->dr.counts;
   AG_HIP(hipMemsetAsync(d_counts, 0, sizeof(int64_t) * N, st));
   if (n > 0) {
@@ -2273,30 +2199,10 @@ int ag_bidder_update(ag_ctx *c, const ag_shading_samples *s, const int32_t *agen
   TrainPlan P0, P1;
   if (int rc = train_plan(c, 0, cnt, trained, P0)) return rc;
   if (int rc = train_plan(c, 1, cnt, trained, P1)) return rc;
-  // device tables (shared by the two launches, rewritten in stream order): exchange
-  // partials [G][2][32] i64; barrier lines [lines][32] u32; blk_agent [G], blk_rank [G],
-  // agent_nblk [N], bar_off [N] i32; win-rate models [N][4] f32 (phase 0 -> phase 1)
-  const size_t gmax = (size_t)std::max(P0.G, P1.G), lmax = (size_t)std::max(P0.T.lines, P1.T.lines);
-  const size_t need_coop = sizeof(int64_t) * 96 * gmax + sizeof(unsigned) * kBarLineWords * lmax +
-                           sizeof(int32_t) * (2 * gmax + 2 * (size_t)N) + sizeof(float) * 4 * N + 64;
-  if (need_coop > w.coop_bytes) {
-    (void)hipFree(w.coop);
-    w.coop = nullptr;
-    w.coop_bytes = 0;
-    AG_HIP(hipMalloc(&w.coop, need_coop));
-    w.coop_bytes = need_coop;
-  }
-  TrainDev D;
-  D.part = (int64_t *)w.coop;
-  D.bar = (unsigned *)(D.part + 96 * gmax);
-  D.bagent = (int32_t *)(D.bar + kBarLineWords * lmax);
-  D.brank = D.bagent + gmax;
-  D.nblk = D.brank + gmax;
-  D.baroff = D.nblk + N;
-  D.wr = (float *)(D.baroff + N);
-  D.noff = d_noff;
-  D.epochs = d_epochs;
-  D.stat = d_stat;
+  const size_t gmax = (size_t)std::max(P0.T.G(), P1.T.G()), lmax = (size_t)std::max(P0.T.lines, P1.T.lines);
+  AG_HIP(agtrain::dev_reserve(&w.coop, &w.coop_bytes, agtrain::layout_bytes(agtrain::train_layout, N, gmax, lmax) + 64));
+  Carve carve(w.coop);
+  const agtrain::TrainTables D = agtrain::train_layout(carve, N, gmax, lmax);
   FitSt *pst = nullptr;
   if (!pipe_slots.empty()) {
     pst = pipe_fitst(c);
@@ -2313,60 +2219,33 @@ int ag_bidder_update(ag_ctx *c, const ag_shading_samples *s, const int32_t *agen
     nz.stride = 0;
     nz.e0 = 0;
     nz.epochs = noise_epochs;
-    const DrRecords R{SR.ctr, SR.val, SR.gam, SR.prop, SR.util, SR.won};
-    if (int rc = pipe_run(c, pipe_slots, cnt, R, SR.eu, SR.d_off, w.counts, pst, nullptr, nz, traces, 3, st)) return rc;
+    if (int rc = pipe_run(c, pipe_slots, cnt, records_of(SR), SR.eu, SR.d_off, w.counts, pst, nullptr, nz, traces, 3, st))
+      return rc;
   }
-  if (int rc = train_launch(c, P0, D, SR, noise, noise_epochs, traces, st)) return rc;
-  if (int rc = train_launch(c, P1, D, SR, noise, noise_epochs, traces, st)) return rc;
+  for (const TrainPlan *P : {&P0, &P1})
+    if (int rc = train_launch(c, *P, D, SR, noise, d_noff, noise_epochs, d_epochs, d_stat, traces, st)) return rc;
   std::vector<int32_t> h(4 * (size_t)N);
   AG_HIP(hipMemcpyAsync(h.data(), d_epochs, sizeof(int32_t) * 4 * N, hipMemcpyDeviceToHost, st));
   AG_HIP(hipStreamSynchronize(st));
-  if (pst) {  // the pipe's learners: epochs, status and (unless out of noise) their models
-    std::vector<FitSt> fs(N);
-    std::vector<float> state(16 * (size_t)N);
+  // k_bidder_train wrote its learners' epochs, status and models; the pipe's are in their FitSt
+  std::vector<FitSt> fs(pst ? N : 0);
+  std::vector<float> state(16 * (size_t)N);
+  std::vector<int32_t> init(N), mode(N);
+  if (pst) {
     AG_HIP(hipMemcpy(fs.data(), pst, sizeof(FitSt) * N, hipMemcpyDeviceToHost));
     AG_HIP(hipMemcpy(state.data(), w.state, sizeof(float) * 16 * N, hipMemcpyDeviceToHost));
-    for (int a : pipe_slots) {
-      const FitSt &f = fs[a];
-      for (int j = 0; j < 3; ++j) h[3 * a + j] = f.ep[j];
-      int stt = f.status;
-      if (f.fit != kFitDone) {  // waits for noise epochs past noise_epochs: not applied
-        stt = -3;
-        h[3 * a + 2] = f.epoch;
-      } else if (stt != 1) {
-        for (int j = 0; j < 4; ++j) state[16 * (size_t)a + j] = f.wr[j];
-        for (int j = 0; j < 12; ++j) state[16 * (size_t)a + 4 + j] = f.pol[j];
-      }
-      h[3 * (size_t)N + a] = stt;
-    }
-    AG_HIP(hipMemcpy(w.state, state.data(), sizeof(float) * 16 * N, hipMemcpyHostToDevice));
   }
-  if (epochs) memcpy(epochs, h.data(), sizeof(int32_t) * 3 * N);
-  if (status) memcpy(status, h.data() + 3 * (size_t)N, sizeof(int32_t) * N);
-  static const char *names[] = {"", "", "ValueLearningBidder", "PolicyLearningBidder", "DoublyRobustBidder"};
-  for (int a = 0; a < N; ++a) {
-    const int bk = c->h_bkind[a];
-    if (h[3 * N + a] == -1)
-      return ag_set_error(AG_ERR_INVALID, "agent %d: %s.update without logs", a, names[bk]);
-    if (h[3 * N + a] == -2)
-      return ag_set_error(AG_ERR_INVALID, "agent %d: %s: NAN DETECTED! in losses (src/Bidder.py:%d)", a, names[bk],
-                          bk == AG_BIDDER_DOUBLY_ROBUST ? 592 : 409);
-  }
-  // from now on the agents bid from what they fitted (src/Bidder.py:321, :430, :612-613):
-  // 1 = the policy, 2 = the win-rate search (ValueLearningBidder 'search'); 0 after the
-  // ValueLearningBidder's no-win fallback (:206-211)
-  std::vector<int32_t> init(N), mode(N);
   AG_HIP(hipMemcpy(init.data(), w.init, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
   AG_HIP(hipMemcpy(mode.data(), w.mode, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
-  for (int a = 0; a < N; ++a) {
-    const int bk = c->h_bkind[a];
-    if ((agents && !agents[a]) || h[3 * N + a] == -3) continue;  // not updated
-    if (bk == AG_BIDDER_DOUBLY_ROBUST || bk == AG_BIDDER_POLICY_LEARNING)
-      init[a] = AG_LEARNER_POLICY;
-    else if (bk == AG_BIDDER_VALUE_LEARNING)
-      init[a] = h[3 * N + a] == 1 ? AG_LEARNER_UNINITIALISED
-                                  : (mode[a] == AG_VL_POLICY ? AG_LEARNER_POLICY : AG_LEARNER_SEARCH);
-  }
+  int rc = AG_OK;
+  for (int a = 0; a < N; ++a)
+    if (trained[a] || pipe_mask[a])
+      rc = apply_fit(c, a, pipe_mask[a] ? &fs[a] : nullptr, mode[a], &state[16 * (size_t)a], &init[a], &h[3 * (size_t)a],
+                     &h[3 * (size_t)N + a], rc);
+  if (pst) AG_HIP(hipMemcpy(w.state, state.data(), sizeof(float) * 16 * N, hipMemcpyHostToDevice));
+  if (epochs) memcpy(epochs, h.data(), sizeof(int32_t) * 3 * N);
+  if (status) memcpy(status, h.data() + 3 * (size_t)N, sizeof(int32_t) * N);
+  if (rc) return rc;  // (the learner flags stay as they were)
   AG_HIP(hipMemcpy(w.init, init.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice));
   learner_flags(c, init.data());
   return AG_OK;
@@ -2396,8 +2275,7 @@ int ag_bidder_rp_begin(ag_ctx *c, const ag_shading_samples *s, const int32_t *ag
   hipStream_t st = (hipStream_t)stream;
   ag_dr_ws &w = c->dr;
   ag_dr_rp &rp = w.rp;
-  std::vector<int32_t> mode(N), mask(N, 0);
-  AG_HIP(hipMemcpy(mode.data(), w.mode, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
+  std::vector<int32_t> mask(N, 0);
   for (int a = 0; a < N; ++a) {
     const int bk = c->h_bkind ? c->h_bkind[a] : -1;
     if (agents && !agents[a]) continue;
@@ -2416,39 +2294,22 @@ int ag_bidder_rp_begin(ag_ctx *c, const ag_shading_samples *s, const int32_t *ag
   T.nblk.assign(N, 0);
   for (int a = 0; a < N; ++a)
     if (mask[a]) T.nblk[a] = (int32_t)std::max<int64_t>(1, (cnt[a] + kRpChunk - 1) / kRpChunk);
-  block_tables(T, [](int nb) { return std::max(1, agcoop::bar_lines(nb)); });
-  const std::vector<int32_t> &nblk = T.nblk, &blk_agent = T.blk_agent, &blk_rank = T.blk_rank, &bar_off = T.bar_off;
-  const int lines = T.lines;
-  const int G = (int)blk_agent.size();
-  if ((size_t)G > rp.cap_g || (size_t)lines > rp.cap_lines || !rp.st || !rp.acc || !rp.tables) {
-    (void)hipFree(rp.st);
-    (void)hipFree(rp.acc);
-    (void)hipFree(rp.tables);
-    rp.st = nullptr;
-    rp.acc = nullptr;
-    rp.tables = nullptr;
-    // capacities zero until every buffer is allocated: a failed allocation leaves the
-    // workspace empty, and the next call allocates it again
-    rp.cap_g = 0;
-    rp.cap_lines = 0;
-    const size_t cap_g = (size_t)G + 64, cap_lines = (size_t)lines + 16;
-    AG_HIP(hipMalloc(&rp.st, sizeof(FitSt) * 2 * (size_t)N));
-    // accumulator rows and barrier lines: [cap_lines][32] each
-    AG_HIP(hipMalloc(&rp.acc, (sizeof(int64_t) + sizeof(unsigned)) * 32 * cap_lines));
-    AG_HIP(hipMalloc(&rp.tables, sizeof(int32_t) * (2 * cap_g + 3 * (size_t)N) + sizeof(int64_t) * 2 * N + 16));
-    rp.cap_g = cap_g;
-    rp.cap_lines = cap_lines;
-  }
-  rp.bar = (unsigned *)(rp.acc + 32 * rp.cap_lines);
-  int32_t *d_bagent = rp.tables, *d_brank = d_bagent + rp.cap_g, *d_nblk = d_brank + rp.cap_g,
-          *d_baroff = d_nblk + N, *d_mask = d_baroff + N;
-  rp.ntot = (int64_t *)(((uintptr_t)(d_mask + N) + 15) & ~(uintptr_t)15);
-  rp.mask = d_mask;
-  AG_HIP(hipMemcpyAsync(d_bagent, blk_agent.data(), sizeof(int32_t) * G, hipMemcpyHostToDevice, st));
-  AG_HIP(hipMemcpyAsync(d_brank, blk_rank.data(), sizeof(int32_t) * G, hipMemcpyHostToDevice, st));
-  AG_HIP(hipMemcpyAsync(d_nblk, nblk.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
-  AG_HIP(hipMemcpyAsync(d_baroff, bar_off.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
-  AG_HIP(hipMemcpyAsync(d_mask, mask.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
+  agtrain::block_tables(T, [](int nb) { return std::max(1, agcoop::bar_lines(nb)); });
+  const int lines = T.lines, G = T.G();
+  // (room for 64 more workgroups and 16 more lines before the buffers grow again)
+  AG_HIP(agtrain::dev_reserve(&rp.st, &rp.st_bytes, sizeof(FitSt) * 2 * (size_t)N));
+  AG_HIP(agtrain::dev_reserve(&rp.acc, &rp.acc_bytes, agtrain::layout_bytes(agtrain::rp_acc_layout, lines, 32),
+                              agtrain::layout_bytes(agtrain::rp_acc_layout, lines + 16, 32)));
+  AG_HIP(agtrain::dev_reserve(&rp.tables, &rp.tables_bytes, agtrain::layout_bytes(agtrain::rp_tables_layout, N, G, 2 * N),
+                              agtrain::layout_bytes(agtrain::rp_tables_layout, N, G + 64, 2 * N)));
+  Carve carve_acc(rp.acc), carve_tables(rp.tables);
+  rp.A = agtrain::rp_acc_layout(carve_acc, lines, 32);
+  rp.T = agtrain::rp_tables_layout(carve_tables, N, G, 2 * N);
+  AG_HIP(hipMemcpyAsync(rp.T.bagent, T.blk_agent.data(), sizeof(int32_t) * G, hipMemcpyHostToDevice, st));
+  AG_HIP(hipMemcpyAsync(rp.T.brank, T.blk_rank.data(), sizeof(int32_t) * G, hipMemcpyHostToDevice, st));
+  AG_HIP(hipMemcpyAsync(rp.T.nblk, T.nblk.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
+  AG_HIP(hipMemcpyAsync(rp.T.baroff, T.bar_off.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
+  AG_HIP(hipMemcpyAsync(rp.T.mask, mask.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
   std::vector<int64_t> nt(2 * (size_t)N);
   for (int a = 0; a < N; ++a) {
     nt[a] = records_total ? records_total[a] : cnt[a];
@@ -2460,10 +2321,10 @@ int ag_bidder_rp_begin(ag_ctx *c, const ag_shading_samples *s, const int32_t *ag
       return ag_set_error(AG_ERR_INVALID, "ag_bidder_rp_begin: agent %d: records_base %lld + %lld local records "
                           "> records_total %lld", a, (long long)nt[N + a], (long long)cnt[a], (long long)nt[a]);
   }
-  AG_HIP(hipMemcpyAsync(rp.ntot, nt.data(), sizeof(int64_t) * 2 * N, hipMemcpyHostToDevice, st));
-  if (lines) AG_HIP(hipMemsetAsync(rp.acc, 0, (sizeof(int64_t) + sizeof(unsigned)) * 32 * rp.cap_lines, st));
+  AG_HIP(hipMemcpyAsync(rp.T.ntot, nt.data(), sizeof(int64_t) * 2 * N, hipMemcpyHostToDevice, st));
+  if (lines) AG_HIP(hipMemsetAsync(rp.acc, 0, carve_acc.bytes(), st));
   AG_HIP(hipMemsetAsync(totals, 0, sizeof(int64_t) * 2 * 32 * (size_t)N, st));
-  hipLaunchKernelGGL(k_rp_init, dim3((N + 255) / 256), dim3(256), 0, st, N, c->d_bkind, w.mode, d_mask, w.state,
+  hipLaunchKernelGGL(k_rp_init, dim3((N + 255) / 256), dim3(256), 0, st, N, c->d_bkind, w.mode, rp.T.mask, w.state,
                      (FitSt *)rp.st, 2);
   AG_HIP(hipGetLastError());
   if (int rc = dr_ws_ready(c)) return rc;  // the Adam table
@@ -2474,12 +2335,11 @@ int ag_bidder_rp_begin(ag_ctx *c, const ag_shading_samples *s, const int32_t *ag
   rp.noise = nullptr;
   rp.noise_n = 0;
   rp.noise_e0 = rp.noise_epochs = 0;
-  rp.n_local = SR.n;
+  rp.recs = SR;
   rp.single = true;
   for (int a = 0; a < N; ++a)
     if (mask[a] && (nt[a] != cnt[a] || nt[N + a] != 0)) rp.single = false;
   rp.active = true;
-  (void)mode;
   return AG_OK;
 }
 
@@ -2502,7 +2362,7 @@ int ag_bidder_rp_run(ag_ctx *c, float *traces, void *stream) {
   std::vector<int64_t> cnt(N + 1);
   std::vector<FitSt> h(N);
   FitSt *S = (FitSt *)rp.st + (size_t)(rp.k & 1) * N;
-  AG_HIP(hipMemcpyAsync(mask.data(), rp.mask, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+  AG_HIP(hipMemcpyAsync(mask.data(), rp.T.mask, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
   AG_HIP(hipMemcpyAsync(cnt.data(), w.counts + N, sizeof(int64_t) * (N + 1), hipMemcpyDeviceToHost, st));
   AG_HIP(hipMemcpyAsync(h.data(), S, sizeof(FitSt) * N, hipMemcpyDeviceToHost, st));
   AG_HIP(hipStreamSynchronize(st));
@@ -2527,14 +2387,12 @@ int ag_bidder_rp_run(ag_ctx *c, float *traces, void *stream) {
       if (!busy) return AG_OK;
     }
   }
-  double *eu = nullptr;
-  const DrRecords R = sorted_view(w, rp.n_local, &eu);
   PipeNoise nz;
   nz.noise = rp.noise;
   nz.stride = rp.noise_n;
   nz.e0 = rp.noise_e0;
   nz.epochs = rp.noise_epochs;
-  return pipe_run(c, slots, n, R, eu, w.counts + N, rp.ntot, S, rp.totals + (size_t)((rp.k + 1) & 1) * 32 * N, nz,
+  return pipe_run(c, slots, n, records_of(rp.recs), rp.recs.eu, rp.recs.d_off, rp.T.ntot, S, rp.totals + (size_t)((rp.k + 1) & 1) * 32 * N, nz,
                   traces, ph0 ? 3 : 2, st);
 }
 
@@ -2558,17 +2416,15 @@ int ag_bidder_rp_epoch(ag_ctx *c, int32_t launches, int64_t *launch_index, float
   hipStream_t st = (hipStream_t)stream;
   ag_dr_ws &w = c->dr;
   ag_dr_rp &rp = w.rp;
-  double *b_eu = nullptr;
-  const DrRecords R = sorted_view(w, rp.n_local, &b_eu);
-  int32_t *d_bagent = rp.tables, *d_brank = d_bagent + rp.cap_g, *d_nblk = d_brank + rp.cap_g, *d_baroff = d_nblk + N;
+  const DrRecords R = records_of(rp.recs);
   FitSt *S = (FitSt *)rp.st;
   for (int32_t l = 0; l < launches; ++l) {
     const int64_t k = rp.k;
     if (rp.G > 0)
-      hipLaunchKernelGGL(k_bidder_epoch, dim3(rp.G), dim3(kDrThreads), 0, st, c->d_bkind, w.mode, w.init, d_bagent,
-                         d_brank, d_nblk, w.counts + N, rp.ntot, rp.ntot + N, R, b_eu, S + (size_t)(k & 1) * N,
+      hipLaunchKernelGGL(k_bidder_epoch, dim3(rp.G), dim3(kDrThreads), 0, st, c->d_bkind, w.mode, w.init, rp.T.bagent,
+                         rp.T.brank, rp.T.nblk, rp.recs.d_off, rp.T.ntot, rp.T.ntot + N, R, rp.recs.eu, S + (size_t)(k & 1) * N,
                          S + (size_t)((k + 1) & 1) * N, rp.totals + (size_t)((k + 1) & 1) * 32 * N,
-                         rp.totals + (size_t)(k & 1) * 32 * N, rp.acc, rp.bar, d_baroff, rp.noise, rp.noise_n,
+                         rp.totals + (size_t)(k & 1) * 32 * N, rp.A.acc, rp.A.bar, rp.T.baroff, rp.noise, rp.noise_n,
                          rp.noise_e0, rp.noise_epochs, c->fit_noise_seed, w.adam_tab, traces);
     AG_HIP(hipGetLastError());
     rp.k = k + 1;
@@ -2607,7 +2463,7 @@ int ag_bidder_rp_end(ag_ctx *c, int32_t *epochs, int32_t *status, void *stream) 
   std::vector<float> state(16 * (size_t)N);
   AG_HIP(hipMemcpyAsync(h.data(), (FitSt *)rp.st + (size_t)(rp.k & 1) * N, sizeof(FitSt) * N, hipMemcpyDeviceToHost,
                         st));
-  AG_HIP(hipMemcpyAsync(mask.data(), rp.mask, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+  AG_HIP(hipMemcpyAsync(mask.data(), rp.T.mask, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
   AG_HIP(hipStreamSynchronize(st));
   rp.active = false;
   for (int a = 0; a < N; ++a)
@@ -2617,29 +2473,12 @@ int ag_bidder_rp_end(ag_ctx *c, int32_t *epochs, int32_t *status, void *stream) 
   AG_HIP(hipMemcpy(state.data(), w.state, sizeof(float) * 16 * N, hipMemcpyDeviceToHost));
   AG_HIP(hipMemcpy(init.data(), w.init, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
   AG_HIP(hipMemcpy(mode.data(), w.mode, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
-  static const char *names[] = {"", "", "ValueLearningBidder", "PolicyLearningBidder", "DoublyRobustBidder"};
   int rc = AG_OK;
   for (int a = 0; a < N; ++a) {
-    if (epochs) epochs[3 * a] = epochs[3 * a + 1] = epochs[3 * a + 2] = 0;
-    if (status) status[a] = 0;
-    if (!mask[a]) continue;
-    if (epochs)
-      for (int j = 0; j < 3; ++j) epochs[3 * a + j] = h[a].ep[j];
-    if (status) status[a] = h[a].status;
-    const int bk = c->h_bkind[a];
-    if (h[a].status == -2 && rc == AG_OK)
-      rc = ag_set_error(AG_ERR_INVALID, "agent %d: %s: NAN DETECTED! in losses (src/Bidder.py:%d)", a, names[bk],
-                        bk == AG_BIDDER_DOUBLY_ROBUST ? 592 : 409);
-    if (h[a].status != 1) {  // the fallback trains nothing (src/Bidder.py:206-211)
-      for (int j = 0; j < 4; ++j) state[16 * (size_t)a + j] = h[a].wr[j];
-      for (int j = 0; j < 12; ++j) state[16 * (size_t)a + 4 + j] = h[a].pol[j];
-    }
-    // from now on the agent bids from what it fitted (ag_bidder_update's rule)
-    if (bk == AG_BIDDER_DOUBLY_ROBUST)
-      init[a] = AG_LEARNER_POLICY;
-    else
-      init[a] = h[a].status == 1 ? AG_LEARNER_UNINITIALISED
-                                 : (mode[a] == AG_VL_POLICY ? AG_LEARNER_POLICY : AG_LEARNER_SEARCH);
+    int32_t ep[3] = {0, 0, 0}, stat = 0;
+    if (mask[a]) rc = apply_fit(c, a, &h[a], mode[a], &state[16 * (size_t)a], &init[a], ep, &stat, rc);
+    if (epochs) memcpy(epochs + 3 * a, ep, sizeof ep);
+    if (status) status[a] = stat;
   }
   AG_HIP(hipMemcpy(w.state, state.data(), sizeof(float) * 16 * N, hipMemcpyHostToDevice));
   AG_HIP(hipMemcpy(w.init, init.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice));

@@ -57,27 +57,30 @@ inline int ag_read_out(const ag_batch_out *p, ag_batch_out *v, const char *who) 
     if (int rc_ = ag_read_out(p, &(v), who)) return rc_; \
   } while (0)
 
+// The trainers' workspaces keep what their layouts carved (after the macros above: its HIP
+// wrappers use them).
+#include "ag_train_host.h"
+
 // LR-TS training workspace (ag_lrts.hip), grown on demand by ag_lrts_update.
 struct ag_lrts_ws {
   int64_t cap = 0;            // samples the bucket arrays hold
   uint32_t *key = nullptr;    // [cap] samples bucketed by agent
   float *x = nullptr;         // [Do][cap]
   int64_t *offsets = nullptr; // [N + 1] bucket offsets, then per-agent cursors [N]
-  double *adam_tab = nullptr; // [2][kLrEpochs]: 1 - 0.9^t, (1 - 0.999^t)^0.5 (host pow)
+  double *adam_tab = nullptr; // [2][kLrEpochs]: agtrain::adam_bias_table
   int32_t *epochs = nullptr;  // [N]
-  void *tables = nullptr;     // workgroup -> (agent, rank) tables + per-agent barriers
-  int64_t *partials = nullptr;  // per-workgroup exact partial sums, 2 epoch parities
-  size_t tab_cap = 0, part_cap = 0, bar_cap = 0;
+  void *tables = nullptr;     // agtrain::lrts_layout
+  int64_t *partials = nullptr;  // agents' combining-tree accumulator rows [lines][144]
+  size_t tables_bytes = 0, partials_bytes = 0;
   int coop_blocks = 0;        // co-resident workgroups of the training kernel
-  int32_t *status = nullptr;  // [1] device-side error flags
   // resumable / record-parallel training (ag_lrts_rp_*): one launch per epoch
   struct {
     bool active = false;
     void *st = nullptr;          // LrSt [2][N], by launch parity
-    int64_t *acc = nullptr;      // combining-tree accumulator rows [lines][144]
-    unsigned *bar = nullptr;     // barrier lines [lines][32]
-    int32_t *tables = nullptr;   // blk_agent [G], blk_rank [G], agent_nblk [N], bar_off [N], mask [N]
-    size_t cap_g = 0, cap_lines = 0;
+    void *acc = nullptr, *tables = nullptr;
+    size_t st_bytes = 0, acc_bytes = 0, tables_bytes = 0;
+    agtrain::RpAcc A{};          // of acc: accumulator rows [lines][144], barrier lines [lines][32]
+    agtrain::RpTables T{};       // of tables
     int G = 0;
     int64_t k = 0;               // launches so far
     int64_t *totals = nullptr;   // the caller's dev int64 [2][N][144]
@@ -89,22 +92,20 @@ struct ag_lrts_ws {
 struct ag_dr_rp {
   bool active = false;
   void *st = nullptr;           // FitSt [2][N], by launch parity
-  int64_t *acc = nullptr;       // agents' combining-tree accumulator rows [lines][32]
-  unsigned *bar = nullptr;      // agents' barrier lines [lines][32]
-  int32_t *tables = nullptr;    // blk_agent [G], blk_rank [G], agent_nblk [N], bar_off [N]
-  int64_t *ntot = nullptr;      // [N] records over all ranks, [N] global index of this rank's first
-  size_t cap_g = 0, cap_lines = 0;
+  void *acc = nullptr, *tables = nullptr;
+  size_t st_bytes = 0, acc_bytes = 0, tables_bytes = 0;
+  agtrain::RpAcc A{};           // of acc: agents' accumulator rows [lines][32], barrier lines [lines][32]
+  agtrain::RpTables T{};        // of tables; ntot: [N] records over all ranks, [N] global index of this rank's first
   int G = 0, lines = 0;
   int64_t k = 0;                // launches so far
   int64_t *totals = nullptr;    // the caller's dev int64 [2][N][32]
   const float *noise = nullptr; // host-drawn rsample window (ag_bidder_rp_noise)
   int64_t noise_n = 0;
   int32_t noise_e0 = 0, noise_epochs = 0;
-  int32_t *mask = nullptr;      // [N] the agents under training (host copy in `agents`)
-  int64_t n_local = 0;
+  agtrain::SortedRecs recs{};   // this rank's records, as ag_bidder_rp_begin sorted them
   bool single = false;          // this rank holds every record (ag_bidder_rp_run allowed)
-  // k_bidder_pipe (ag_bidder_rp_run, ag_bidder_update): slot tables, tree rows / barrier
-  // lines, its own FitSt [N] for ag_bidder_update
+  // k_bidder_pipe (ag_bidder_rp_run, ag_bidder_update): two agtrain::pipe_layout, its own
+  // FitSt [N] for ag_bidder_update
   void *pipe = nullptr;
   size_t pipe_bytes = 0;
   void *pipe_st = nullptr;      // FitSt [N] of ag_bidder_update's pipe run
@@ -113,16 +114,15 @@ struct ag_dr_rp {
 
 // DoublyRobustBidder workspace (ag_dr.hip)
 struct ag_dr_ws {
-  void *buf = nullptr;          // records in log order (ctr, value, gamma, prop, util, est_util,
-                                // won), sort keys / indices, hipcub temp
+  void *buf = nullptr;          // agtrain::sorted_layout
   size_t buf_bytes = 0;
   int64_t *counts = nullptr;    // [N] counts, [N + 1] offsets
-  double *adam_tab = nullptr;   // [2][32768] Adam bias corrections (libm pow)
+  double *adam_tab = nullptr;   // [2][32768]: agtrain::adam_bias_table
   float *state = nullptr;       // [N][16]: win-rate w0 w1 w2 b, policy (12)
   int32_t *init = nullptr;      // [N] AG_LEARNER_*: what the agent bids from
   int32_t *mode = nullptr;      // [N] ValueLearningBidder inference / PolicyLearningBidder loss
   int64_t *scratch = nullptr;   // [N] noise offsets + [N][4] epochs / status
-  void *coop = nullptr;         // trainer workgroup tables, barriers, exchange partials
+  void *coop = nullptr;         // agtrain::train_layout
   size_t coop_bytes = 0;
   int coop_blocks = 0;          // co-resident workgroups of k_bidder_train<1>
   int coop_blocks0 = 0;         // co-resident workgroups of k_bidder_train<0>

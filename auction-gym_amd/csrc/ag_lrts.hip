@@ -605,11 +605,7 @@ TrainKernel pick_train(int Do) {
   }
 }
 
-int grid_over(int64_t n) {
-  int64_t g = (n + kLrThreads - 1) / kLrThreads;
-  if (g > 4096) g = 4096;
-  return (int)(g < 1 ? 1 : g);
-}
+int grid_over(int64_t n) { return agtrain::grid_over(n, kLrThreads); }
 
 int check_store(const ag_ctx *c, const ag_lrts_samples *s, const char *who) {
   if (!c || !s) return ag_set_error(AG_ERR_INVALID, "%s: null argument", who);
@@ -669,21 +665,12 @@ int ag_lrts_collect(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch_
 static int bucket_samples(ag_ctx *c, const ag_lrts_samples *s, hipStream_t st, const char *who) {
   const int N = c->shape.num_agents, Do = c->shape.obs_embedding_size + 1;
   uint64_t n = 0;
-  AG_HIP(hipMemcpyAsync(&n, s->count, sizeof n, hipMemcpyDeviceToHost, st));
-  AG_HIP(hipStreamSynchronize(st));
-  if ((int64_t)n > s->capacity)
-    return ag_set_error(AG_ERR_INVALID, "%s: %llu won samples overflowed the store (capacity %lld)",
-                        who, (unsigned long long)n, (long long)s->capacity);
+  if (int rc = agtrain::read_store_count(s->count, s->capacity, who, "won samples", st, &n)) return rc;
   ag_lrts_ws &w = c->lrts;
   if (!w.adam_tab) {
-    double *tab = new double[2 * kLrEpochs];
-    for (int t = 0; t < kLrEpochs; ++t) {  // torch.optim.Adam: Python floats, libm pow
-      tab[t] = 1.0 - pow(0.9, (double)(t + 1));
-      tab[kLrEpochs + t] = pow(1.0 - pow(0.999, (double)(t + 1)), 0.5);
-    }
-    hipError_t e = hipMalloc(&w.adam_tab, sizeof(double) * 2 * kLrEpochs);
-    if (e == hipSuccess) e = hipMemcpy(w.adam_tab, tab, sizeof(double) * 2 * kLrEpochs, hipMemcpyHostToDevice);
-    delete[] tab;
+    const std::vector<double> tab = agtrain::adam_bias_table(kLrEpochs);
+    hipError_t e = hipMalloc(&w.adam_tab, sizeof(double) * tab.size());
+    if (e == hipSuccess) e = hipMemcpy(w.adam_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc(&w.offsets, sizeof(int64_t) * (3 * (size_t)N + 1));
     if (e == hipSuccess) e = hipMalloc(&w.epochs, sizeof(int32_t) * N);
     if (e != hipSuccess) {
@@ -691,18 +678,14 @@ static int bucket_samples(ag_ctx *c, const ag_lrts_samples *s, hipStream_t st, c
       return ag_set_error(AG_ERR_HIP, "%s: workspace: %s", who, hipGetErrorString(e));
     }
   }
-  if ((int64_t)n > w.cap) {
-    (void)hipFree(w.key);
-    (void)hipFree(w.x);
-    w.key = nullptr;
-    w.x = nullptr;
+  if ((int64_t)n > w.cap) {  // key and x share the capacity (x's row stride): both again
     const int64_t cap = (int64_t)n + ((int64_t)n >> 2) + 1024;
-    hipError_t e = hipMalloc(&w.key, sizeof(uint32_t) * cap);
-    if (e == hipSuccess) e = hipMalloc(&w.x, sizeof(float) * (size_t)Do * cap);
-    if (e != hipSuccess) {
-      w.cap = 0;
-      return ag_set_error(AG_ERR_HIP, "%s: sample workspace: %s", who, hipGetErrorString(e));
-    }
+    size_t none = 0;
+    w.cap = 0;
+    hipError_t e = agtrain::dev_reserve(&w.key, &none, sizeof(uint32_t) * cap);
+    none = 0;
+    if (e == hipSuccess) e = agtrain::dev_reserve(&w.x, &none, sizeof(float) * (size_t)Do * cap);
+    if (e != hipSuccess) return ag_set_error(AG_ERR_HIP, "%s: sample workspace: %s", who, hipGetErrorString(e));
     w.cap = cap;
   }
   int64_t *counts = w.offsets + N + 1, *cursors = counts + N;
@@ -738,123 +721,46 @@ int ag_lrts_update(ag_ctx *c, const ag_lrts_samples *s, int32_t *epochs, float *
   if (int rc = bucket_samples(c, s, st, "ag_lrts_update")) return rc;
   ag_lrts_ws &w = c->lrts;
   // agents' sample counts -> workgroups per agent (kLrCache samples per lane each)
-  int64_t *h_off = new int64_t[N + 1];
-  hipError_t e = hipMemcpyAsync(h_off, w.offsets, sizeof(int64_t) * (N + 1), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    delete[] h_off;
-    return ag_set_error(AG_ERR_HIP, "ag_lrts_update: %s", hipGetErrorString(e));
-  }
+  std::vector<int64_t> h_off((size_t)N + 1);
+  AG_HIP(hipMemcpyAsync(h_off.data(), w.offsets, sizeof(int64_t) * (N + 1), hipMemcpyDeviceToHost, st));
+  AG_HIP(hipStreamSynchronize(st));
   const size_t lds = sizeof(int64_t) * (size_t)K * Do * kAccStride;
   AG_HIP(hipFuncSetAttribute((const void *)train, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  if (!w.coop_blocks) {
-    int per_cu = 0, cus = 0;
-    AG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)train, kLrThreads, lds));
-    AG_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-    w.coop_blocks = per_cu * cus > 0 ? per_cu * cus : 1;
-  }
-  std::vector<int32_t> nblk(N, 0), blk_agent, blk_rank;
-  std::vector<int64_t> pbase(N, 0);
-  int64_t want = 0;
-  int agents = 0;
+  AG_HIP(agtrain::resident_blocks((const void *)train, kLrThreads, lds, c->device, &w.coop_blocks));
+  agtrain::BlockTables T;
+  T.nblk.assign(N, 0);
   const int64_t chunk = c->lrts_chunk > 0 ? c->lrts_chunk : (int64_t)kLrCache * kLrThreads;
   for (int a = 0; a < N; ++a) {
     const int64_t na = h_off[a + 1] - h_off[a];
     if (c->h_akind[a] != AG_ALLOCATOR_LRTS || na < 2) continue;
-    nblk[a] = (int32_t)((na + chunk - 1) / chunk);
-    want += nblk[a];
-    ++agents;
+    T.nblk[a] = (int32_t)((na + chunk - 1) / chunk);
   }
-  delete[] h_off;
-  if (want > w.coop_blocks) {  // more samples than the resident grid caches: share it out
-    const double f = (double)w.coop_blocks / (double)want;
-    want = 0;
-    for (int a = 0; a < N; ++a)
-      if (nblk[a] > 0) {
-        nblk[a] = (int32_t)(nblk[a] * f) > 1 ? (int32_t)(nblk[a] * f) : 1;
-        want += nblk[a];
-      }
-    // the floor stops at 1, so many agents of one workgroup can keep the total above the
-    // resident grid: then every agent trains on one workgroup (a plain launch of any size;
-    // the stream loop takes any n)
-    if (want > w.coop_blocks) {
-      for (int a = 0; a < N; ++a)
-        if (nblk[a] > 1) nblk[a] = 1;
-      want = agents;
-    }
-  }
-  int64_t pwords = 0;
-  int lines = 0;
-  std::vector<int32_t> bar_off(N, 0);
-  bool multi = false;
-  for (int a = 0; a < N; ++a) {
-    bar_off[a] = lines;
-    lines += agcoop::bar_lines(nblk[a]);
-    pbase[a] = pwords;
-    pwords += (int64_t)agcoop::bar_lines(nblk[a]) * kLrAccStride;
-    multi |= nblk[a] > 1;
-    for (int r = 0; r < nblk[a]; ++r) {
-      blk_agent.push_back(a);
-      blk_rank.push_back(r);
-    }
-  }
+  agtrain::share_out(T.nblk, w.coop_blocks);  // more samples than the resident grid caches
+  agtrain::block_tables(T, [](int nb) { return agcoop::bar_lines(nb); });
+  const int G = T.G(), lines = T.lines;
+  const int64_t pwords = (int64_t)lines * kLrAccStride;  // accumulator rows, one per barrier line
+  std::vector<int64_t> pbase(N);
+  for (int a = 0; a < N; ++a) pbase[a] = (int64_t)T.bar_off[a] * kLrAccStride;
   AG_HIP(hipMemsetAsync(w.epochs, 0, sizeof(int32_t) * N, st));
-  const int G = (int)blk_agent.size();
   if (G > 0) {
-    if (multi && G > w.coop_blocks)
-      return ag_set_error(AG_ERR_UNSUPPORTED, "ag_lrts_update: %d agents need more co-resident workgroups "
-                                              "(%d) than the device holds (%d)", agents, G, w.coop_blocks);
-    if ((size_t)G > w.tab_cap || (size_t)pwords > w.part_cap || (size_t)lines > w.bar_cap) {
-      (void)hipFree(w.tables);
-      (void)hipFree(w.partials);
-      w.tables = nullptr;
-      w.partials = nullptr;
-      w.tab_cap = (size_t)G + 256;
-      w.part_cap = (size_t)pwords + 4096;
-      w.bar_cap = (size_t)lines + 64;
-      hipError_t e2 = hipMalloc(&w.tables, sizeof(int64_t) * (w.tab_cap + 2 * (size_t)N) + sizeof(int32_t) * N +
-                                               sizeof(unsigned) * agcoop::kBarLineWords * w.bar_cap);
-      if (e2 == hipSuccess) e2 = hipMalloc(&w.partials, sizeof(int64_t) * w.part_cap);
-      if (e2 != hipSuccess) {
-        w.tab_cap = w.part_cap = w.bar_cap = 0;
-        return ag_set_error(AG_ERR_HIP, "ag_lrts_update: tables: %s", hipGetErrorString(e2));
-      }
-    }
-    // tables: blk_agent [G] i32, blk_rank [G] i32, agent_nblk [N] i32, agent_pbase [N] i64,
-    // bar_off [N] i32, barrier lines [lines][32] u32 (all inside w.tables)
-    char *tb = (char *)w.tables;
-    int32_t *d_bagent = (int32_t *)tb;
-    int32_t *d_brank = d_bagent + w.tab_cap;
-    int32_t *d_nblk = d_brank + w.tab_cap;
-    int64_t *d_pbase = (int64_t *)(d_nblk + 2 * (size_t)N);  // 8-B aligned (even count of i32 before)
-    int32_t *d_baroff = (int32_t *)(d_pbase + N);
-    unsigned *d_bar = (unsigned *)(d_baroff + N);
-    AG_HIP(hipMemcpyAsync(d_bagent, blk_agent.data(), sizeof(int32_t) * G, hipMemcpyHostToDevice, st));
-    AG_HIP(hipMemcpyAsync(d_brank, blk_rank.data(), sizeof(int32_t) * G, hipMemcpyHostToDevice, st));
-    AG_HIP(hipMemcpyAsync(d_nblk, nblk.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
-    AG_HIP(hipMemcpyAsync(d_pbase, pbase.data(), sizeof(int64_t) * N, hipMemcpyHostToDevice, st));
-    AG_HIP(hipMemcpyAsync(d_baroff, bar_off.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
-    if (lines) AG_HIP(hipMemsetAsync(d_bar, 0, sizeof(unsigned) * agcoop::kBarLineWords * lines, st));
+    // (room for 256 more workgroups, 64 more lines and 4096 more words before the buffers grow again)
+    hipError_t e = agtrain::dev_reserve(&w.tables, &w.tables_bytes, agtrain::layout_bytes(agtrain::lrts_layout, N, G, lines),
+                                        agtrain::layout_bytes(agtrain::lrts_layout, N, G + 256, lines + 64));
+    if (e == hipSuccess)
+      e = agtrain::dev_reserve(&w.partials, &w.partials_bytes, sizeof(int64_t) * pwords, sizeof(int64_t) * (pwords + 4096));
+    if (e != hipSuccess) return ag_set_error(AG_ERR_HIP, "ag_lrts_update: tables: %s", hipGetErrorString(e));
+    agtrain::Carve carve(w.tables);
+    const agtrain::LrtsTables D = agtrain::lrts_layout(carve, N, G, lines);
+    AG_HIP(hipMemcpyAsync(D.bagent, T.blk_agent.data(), sizeof(int32_t) * G, hipMemcpyHostToDevice, st));
+    AG_HIP(hipMemcpyAsync(D.brank, T.blk_rank.data(), sizeof(int32_t) * G, hipMemcpyHostToDevice, st));
+    AG_HIP(hipMemcpyAsync(D.nblk, T.nblk.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
+    AG_HIP(hipMemcpyAsync(D.pbase, pbase.data(), sizeof(int64_t) * N, hipMemcpyHostToDevice, st));
+    AG_HIP(hipMemcpyAsync(D.baroff, T.bar_off.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
+    if (lines) AG_HIP(hipMemsetAsync(D.bar, 0, sizeof(unsigned) * agcoop::kBarLineWords * lines, st));
     if (pwords) AG_HIP(hipMemsetAsync(w.partials, 0, sizeof(int64_t) * pwords, st));  // accumulator rows
-    int Kv = K;
-    const int32_t *cbagent = d_bagent, *cbrank = d_brank, *cnblk = d_nblk;
-    const int64_t *cpbase = d_pbase, *coffsets = w.offsets;
-    const uint32_t *ckey = w.key;
-    const float *cx = w.x;
-    int64_t ccap = w.cap;
-    float *gm = c->d_tsm, *gq = c->d_tsq, *gpm = c->d_tsprev;
-    const double *ctab = w.adam_tab;
-    int32_t *cep = w.epochs;
-    float *ctr = loss_trace;
-    int64_t *cpart = w.partials;
-    unsigned *cbar = d_bar;
-    const int32_t *cbaroff = d_baroff;
-    void *args[] = {&Kv, &cbagent, &cbrank, &cnblk, &cpbase, &coffsets, &ckey, &cx, &ccap, &gm, &gq, &gpm,
-                    &ctab, &cep, &ctr, &cpart, &cbar, &cbaroff};
-    if (multi)  // workgroups of one agent wait for each other: they must all be resident
-      AG_HIP(hipLaunchCooperativeKernel((const void *)train, dim3(G), dim3(kLrThreads), args, (unsigned)lds, st));
-    else
-      AG_HIP(hipLaunchKernel((const void *)train, dim3(G), dim3(kLrThreads), args, lds, st));
+    AG_HIP(agtrain::launch_group(train, T.multi(), G, kLrThreads, lds, st, K, D.bagent, D.brank, D.nblk, D.pbase,
+                                 w.offsets, w.key, w.x, w.cap, c->d_tsm, c->d_tsq, c->d_tsprev, w.adam_tab, w.epochs,
+                                 loss_trace, w.partials, D.bar, D.baroff));
   }
   if (epochs) {
     AG_HIP(hipMemcpyAsync(epochs, w.epochs, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
@@ -885,54 +791,37 @@ int ag_lrts_rp_begin(ag_ctx *c, const ag_lrts_samples *s, const int32_t *agents,
   // agents trained: LR-TS allocators in the mask with >= 2 won samples over all ranks (the
   // reference skips the update below that, src/BidderAllocation.py:33-34)
   constexpr int64_t kRpChunk = 2048;
-  std::vector<int32_t> mask(N, 0), nblk(N, 0), blk_agent, blk_rank, bar_off(N, 0);
-  int lines = 0;
+  std::vector<int32_t> mask(N, 0);
+  agtrain::BlockTables T;
+  T.nblk.assign(N, 0);
   for (int a = 0; a < N; ++a) {
     const int64_t na = off[a + 1] - off[a], nt = samples_total ? samples_total[a] : na;
     if (c->h_akind[a] != AG_ALLOCATOR_LRTS || (agents && !agents[a]) || nt < 2) continue;
     mask[a] = 1;
-    nblk[a] = (int32_t)std::max<int64_t>(1, (na + kRpChunk - 1) / kRpChunk);
-    bar_off[a] = lines;
-    lines += std::max(1, agcoop::bar_lines(nblk[a]));
-    for (int r = 0; r < nblk[a]; ++r) {
-      blk_agent.push_back(a);
-      blk_rank.push_back(r);
-    }
+    T.nblk[a] = (int32_t)std::max<int64_t>(1, (na + kRpChunk - 1) / kRpChunk);
   }
-  const int G = (int)blk_agent.size();
-  if ((size_t)G > rp.cap_g || (size_t)lines > rp.cap_lines || !rp.st || !rp.acc || !rp.tables) {
-    (void)hipFree(rp.st);
-    (void)hipFree(rp.acc);
-    (void)hipFree(rp.tables);
-    rp.st = nullptr;
-    rp.acc = nullptr;
-    rp.tables = nullptr;
-    // capacities zero until every buffer is allocated: a failed allocation leaves the
-    // workspace empty, and the next call allocates it again
-    rp.cap_g = 0;
-    rp.cap_lines = 0;
-    const size_t cap_g = (size_t)G + 64, cap_lines = (size_t)lines + 16;
-    AG_HIP(hipMalloc(&rp.st, sizeof(LrSt) * 2 * (size_t)N));
-    AG_HIP(hipMalloc(&rp.acc, sizeof(int64_t) * kLrAccStride * cap_lines + sizeof(unsigned) * 32 * cap_lines));
-    AG_HIP(hipMalloc(&rp.tables, sizeof(int32_t) * (2 * cap_g + 3 * (size_t)N)));
-    rp.cap_g = cap_g;
-    rp.cap_lines = cap_lines;
-  }
-  rp.bar = (unsigned *)(rp.acc + kLrAccStride * rp.cap_lines);
-  int32_t *d_bagent = rp.tables, *d_brank = d_bagent + rp.cap_g, *d_nblk = d_brank + rp.cap_g,
-          *d_baroff = d_nblk + N, *d_mask = d_baroff + N;
+  agtrain::block_tables(T, [](int nb) { return std::max(1, agcoop::bar_lines(nb)); });
+  const int G = T.G(), lines = T.lines;
+  // (room for 64 more workgroups and 16 more lines before the buffers grow again)
+  AG_HIP(agtrain::dev_reserve(&rp.st, &rp.st_bytes, sizeof(LrSt) * 2 * (size_t)N));
+  AG_HIP(agtrain::dev_reserve(&rp.acc, &rp.acc_bytes, agtrain::layout_bytes(agtrain::rp_acc_layout, lines, kLrAccStride),
+                              agtrain::layout_bytes(agtrain::rp_acc_layout, lines + 16, kLrAccStride)));
+  AG_HIP(agtrain::dev_reserve(&rp.tables, &rp.tables_bytes, agtrain::layout_bytes(agtrain::rp_tables_layout, N, G, 0),
+                              agtrain::layout_bytes(agtrain::rp_tables_layout, N, G + 64, 0)));
+  agtrain::Carve carve_acc(rp.acc), carve_tables(rp.tables);
+  rp.A = agtrain::rp_acc_layout(carve_acc, lines, kLrAccStride);
+  rp.T = agtrain::rp_tables_layout(carve_tables, N, G, 0);
   if (G) {
-    AG_HIP(hipMemcpyAsync(d_bagent, blk_agent.data(), sizeof(int32_t) * G, hipMemcpyHostToDevice, st));
-    AG_HIP(hipMemcpyAsync(d_brank, blk_rank.data(), sizeof(int32_t) * G, hipMemcpyHostToDevice, st));
+    AG_HIP(hipMemcpyAsync(rp.T.bagent, T.blk_agent.data(), sizeof(int32_t) * G, hipMemcpyHostToDevice, st));
+    AG_HIP(hipMemcpyAsync(rp.T.brank, T.blk_rank.data(), sizeof(int32_t) * G, hipMemcpyHostToDevice, st));
   }
-  AG_HIP(hipMemcpyAsync(d_nblk, nblk.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
-  AG_HIP(hipMemcpyAsync(d_baroff, bar_off.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
-  AG_HIP(hipMemcpyAsync(d_mask, mask.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
-  AG_HIP(hipMemsetAsync(rp.acc, 0, sizeof(int64_t) * kLrAccStride * rp.cap_lines + sizeof(unsigned) * 32 * rp.cap_lines,
-                        st));
+  AG_HIP(hipMemcpyAsync(rp.T.nblk, T.nblk.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
+  AG_HIP(hipMemcpyAsync(rp.T.baroff, T.bar_off.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
+  AG_HIP(hipMemcpyAsync(rp.T.mask, mask.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
+  if (lines) AG_HIP(hipMemsetAsync(rp.acc, 0, carve_acc.bytes(), st));
   AG_HIP(hipMemsetAsync(totals, 0, sizeof(int64_t) * 2 * kLrAccStride * (size_t)N, st));
   AG_HIP(hipMemsetAsync(w.epochs, 0, sizeof(int32_t) * N, st));
-  hipLaunchKernelGGL(k_lrts_rp_init, dim3(N), dim3(64), 0, st, N, K * Do, d_mask, c->d_tsm, (LrSt *)rp.st);
+  hipLaunchKernelGGL(k_lrts_rp_init, dim3(N), dim3(64), 0, st, N, K * Do, rp.T.mask, c->d_tsm, (LrSt *)rp.st);
   AG_HIP(hipGetLastError());
   const size_t lds = sizeof(int64_t) * (size_t)K * Do * kAccStride;
   AG_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -952,16 +841,15 @@ int ag_lrts_rp_epoch(ag_ctx *c, int32_t launches, int64_t *launch_index, void *s
   auto &rp = w.rp;
   EpochKernel kern = pick_epoch(Do);
   const size_t lds = sizeof(int64_t) * (size_t)K * Do * kAccStride;
-  int32_t *d_bagent = rp.tables, *d_brank = d_bagent + rp.cap_g, *d_nblk = d_brank + rp.cap_g, *d_baroff = d_nblk + N;
   LrSt *S = (LrSt *)rp.st;
   hipStream_t st = (hipStream_t)stream;
   for (int32_t l = 0; l < launches; ++l) {
     const int64_t k = rp.k;
     if (rp.G > 0)
-      hipLaunchKernelGGL(kern, dim3(rp.G), dim3(kLrThreads), lds, st, K, d_bagent, d_brank, d_nblk, w.offsets, w.key,
+      hipLaunchKernelGGL(kern, dim3(rp.G), dim3(kLrThreads), lds, st, K, rp.T.bagent, rp.T.brank, rp.T.nblk, w.offsets, w.key,
                          w.x, w.cap, c->d_tsm, c->d_tsq, c->d_tsprev, w.adam_tab, w.epochs, S + (size_t)(k & 1) * N,
                          S + (size_t)((k + 1) & 1) * N, rp.totals + (size_t)((k + 1) & 1) * kLrAccStride * N,
-                         rp.totals + (size_t)(k & 1) * kLrAccStride * N, rp.acc, rp.bar, d_baroff);
+                         rp.totals + (size_t)(k & 1) * kLrAccStride * N, rp.A.acc, rp.A.bar, rp.T.baroff);
     AG_HIP(hipGetLastError());
     rp.k = k + 1;
   }

@@ -65,6 +65,20 @@ def test_ctypes_structs_match_the_c_header(tmp_path):
         assert cls().struct_size == ctypes.sizeof(cls)
 
 
+def test_trainers_host_planner(tmp_path):
+    """tests/host/train_host_check.cpp: the trainers' workgroup tables, the share-out of the
+    resident grid and every device-buffer layout (csrc/ag_train_host.h, its part without HIP),
+    built by g++ with AddressSanitizer and UBSan (their runtimes linked statically: the program
+    does not depend on what else the loader brings in) and run as a program of its own."""
+    exe = tmp_path / "train_host_check"
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-g", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan",
+                    "-I", os.path.join(ROOT, "auction-gym_amd", "csrc"),
+                    "-o", str(exe), os.path.join(ROOT, "tests", "host", "train_host_check.cpp")], check=True)
+    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stdout.strip() == "train_host_check: ok", run.stdout + run.stderr
+
+
 def test_counters_to_double_host_helper():
     from auctiongym_amd import _lib
     L = _lib.load()
