@@ -17,6 +17,12 @@ samples of LR-TS agents are collected on the device after every batch
 (ag_lrts_collect), and the first LR-TS agent's update() trains every LR-TS agent of the
 auction in one launch (ag_lrts_update; the agents' updates are independent, so batching
 them is the reference's per-agent loop, src/main.py:127-152).
+
+Several slots (max_slots > 1; src/main.py hard-codes 1, src/Auction.py:30, :60-74 are written for
+more): a round draws its slot count and one click per winner (replay.draw_round_slots) and runs
+through ag_simulate_slots. Populations without learners only -- OracleAllocator + TruthfulBidder
+agents with memory = 0: the record collectors that feed Agent.update do not read multi-slot
+rounds yet.
 """
 import warnings
 
@@ -26,7 +32,8 @@ import torch
 from . import Agent as _agent_mod
 from . import _lib
 from .engine import TORCH_NORMAL_AVX2, AuctionEngine
-from .replay import draw_round, draw_round_population, draw_rounds_native, draw_rounds_native_population
+from .replay import (draw_round, draw_round_population, draw_round_slots, draw_rounds_native,
+                     draw_rounds_native_population, draw_rounds_native_slots)
 
 C = _agent_mod.C
 
@@ -62,8 +69,11 @@ class Auction:
         self.embedding_var = embedding_var
         self.obs_embedding_size = obs_embedding_size
         self.num_participants_per_round = num_participants_per_round
-        if max_slots != 1:
-            raise NotImplementedError("max_slots must be 1 (src/main.py:37)")
+        if isinstance(max_slots, bool) or int(max_slots) != max_slots or max_slots < 1:
+            raise ValueError(f"max_slots must be a positive integer (max_slots={max_slots!r})")
+        if max_slots > _lib.MAX_SLOTS:
+            raise NotImplementedError(f"max_slots = {max_slots}: at most {_lib.MAX_SLOTS} slots are built")
+        self._slots = max_slots > 1  # several slots: ag_simulate_slots
 
         # each agent's own num_items (src/main.py:61,66): catalogues padded to the largest K
         # with value-0 rows (ag_set_agent_items)
@@ -81,8 +91,14 @@ class Auction:
         bk = np.array([a.bidder.kind for a in agents], np.int32)
         self._shading = bk != _lib.BIDDER_TRUTHFUL
         self._lrts = ak == _lib.ALLOCATOR_LRTS
+        if self._slots and ((ak == _lib.ALLOCATOR_LRTS).any() or (bk != _lib.BIDDER_TRUTHFUL).any()
+                            or any(a.memory != 0 for a in agents)):
+            raise NotImplementedError(
+                f"max_slots = {max_slots} with learning agents or Agent(memory > 0): log-fed updates from "
+                "multi-slot rounds are not built (the LR-TS and shading record collectors read one-slot rounds)")
         self._engine = eng = AuctionEngine(N, num_participants_per_round, K, embedding_size,
-                                           obs_embedding_size, allocation.code, embedding_var)
+                                           obs_embedding_size, allocation.code, embedding_var,
+                                           max_slots=int(max_slots))
         pg = np.array([getattr(a.bidder, "prev_gamma", 1.0) for a in agents], np.float64)
         gs = np.array([getattr(a.bidder, "gamma_sigma", 1.0) for a in agents], np.float64)
         eng.set_agent_params(ak, bk, pg if self._shading.any() else None,
@@ -170,6 +186,10 @@ class Auction:
     # ------------------------------------------------------------------ rounds
     def _draw_round(self):
         N, P = len(self.agents), self.num_participants_per_round
+        if self._slots:  # (no learners: nothing else draws)
+            self._pending.append(draw_round_slots(self.rng, N, P, self.embedding_size, self.embedding_var,
+                                                  self.max_slots))
+            return
         if not (self._shading.any() or (self._lrts.any() and self._ts)):
             ctx, part, u = draw_round(self.rng, N, P, self.embedding_size, self.embedding_var,
                                       self.max_slots)
@@ -245,6 +265,15 @@ class Auction:
             return
         self._flush()
         N, P = len(self.agents), self.num_participants_per_round
+        if self._slots:
+            d = self._engine.device
+            for lo in range(0, B, self.NATIVE_ROUNDS):
+                n = min(self.NATIVE_ROUNDS, B - lo)
+                ctx, part, _, ns, us = draw_rounds_native_slots(self.rng, n, N, P, self.embedding_size,
+                                                                self.embedding_var, self.max_slots)
+                self._run_slots({"ctx": torch.from_numpy(ctx).to(d), "part": torch.from_numpy(part).to(d)},
+                                torch.from_numpy(ns).to(d), torch.from_numpy(us).to(d))
+            return
         shading, models, policy, search = self._population_draws()
         torch_or_grid = (any(m is not None for m in models) or (policy is not None and any(policy))
                          or (search is not None and any(search)))
@@ -279,6 +308,9 @@ class Auction:
 
     def simulate_synthetic(self, B, seed, first_auction=0):
         """B rounds with on-device Philox inputs (throughput mode; parity via the oracle)."""
+        if self._slots:
+            raise NotImplementedError("synthetic inputs for multi-slot rounds are not built (ag_generate draws "
+                                      "no slot counts)")
         self._settle_lrts()
         self._flush()
         eng = self._engine
@@ -304,6 +336,12 @@ class Auction:
         d, P = self._engine.device, self.num_participants_per_round
         rows, self._pending = self._pending, []
         B = len(rows)
+        if self._slots:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d)  # noqa: E731
+            self._run_slots({"ctx": up(np.stack([r[0] for r in rows], axis=1)),
+                             "part": up(np.stack([r[1] for r in rows], axis=1).astype(np.int32))},
+                            up(np.array([r[2] for r in rows], np.int32)), up(np.stack([r[3] for r in rows], axis=1)))
+            return
         ctx = np.empty((self.embedding_size, B))
         part = np.empty((P, B), np.int32)
         u = np.empty(B)
@@ -356,6 +394,30 @@ class Auction:
             if sl_out is not out:
                 for k, v in out.items():
                     v[..., lo:hi].copy_(sl_out[k])
+        self._account(cnt, inp, out, B)
+
+    def _run_slots(self, inp, num_slots, u_slots):
+        """A batch of multi-slot rounds (ag_simulate_slots): inp ctx [E][B], part [P][B]; num_slots
+        [B]; u_slots [min(max_slots, P)][B]."""
+        eng = self._engine
+        B = num_slots.shape[0]
+        out = eng.alloc_slot_outputs(B)
+        cnt = eng.new_counters()
+        max_b = 2048 * 8192
+        for lo in range(0, B, max_b):
+            hi = min(B, lo + max_b)
+            if hi - lo == B:
+                eng.simulate_slots(inp, num_slots, u_slots, out, cnt)
+                continue
+            sl_out = {k: torch.empty(v[..., lo:hi].shape, dtype=v.dtype, device=v.device) for k, v in out.items()}
+            eng.simulate_slots({k: v[..., lo:hi].contiguous() for k, v in inp.items()},
+                               num_slots[lo:hi].contiguous(), u_slots[:, lo:hi].contiguous(), sl_out, cnt)
+            for k, v in out.items():
+                v[..., lo:hi].copy_(sl_out[k])
+        self._account(cnt, inp, out, B)
+
+    def _account(self, cnt, inp, out, B):
+        """A batch's exact counters into the agents' sums and the revenue; its outputs kept as logs."""
         limbs = cnt.cpu().numpy()
         paid = 0
         for a, agent in enumerate(self.agents):

@@ -49,8 +49,10 @@ EXPORTS = ("ag_create", "ag_destroy", "ag_set_agent_kinds", "ag_set_agent_params
            "ag_abi_version", "ag_ts_noise_index", "ag_generate_ts_noise_compact", "ag_torch_normal_epochs",
            "ag_bidder_rp_begin", "ag_bidder_rp_epoch", "ag_bidder_rp_run", "ag_bidder_rp_noise", "ag_bidder_rp_poll", "ag_bidder_rp_end",
            "ag_lrts_rp_begin", "ag_lrts_rp_epoch", "ag_lrts_rp_poll", "ag_lrts_rp_end", "ag_empirical_update_agents",
-           "ag_coop_selftest", "ag_div_selftest")
+           "ag_coop_selftest", "ag_div_selftest",
+           "ag_simulate_slots", "ag_allocate_slots", "ag_replay_draw_slots", "ag_replay_draw_population_slots")
 ABI_VERSION = 17
+MAX_SLOTS = 8  # AG_MAX_SLOTS
 LEARNER_UNINITIALISED, LEARNER_POLICY, LEARNER_SEARCH = 0, 1, 2
 VL_SEARCH, VL_POLICY = 0, 1
 PL_LOSSES = {"REINFORCE": 0, "REINFORCE_offpolicy": 1, "TRPO": 2, "PPO": 3}
@@ -88,6 +90,16 @@ class AgBatchOut(_Sized):
                 ("true_ctr", ctypes.c_void_p), ("best_ev", ctypes.c_void_p),
                 ("gamma", ctypes.c_void_p), ("propensity", ctypes.c_void_p),
                 ("winner_outcome", ctypes.c_void_p)]  # ABI 17
+
+
+class AgSlotsOut(_Sized):
+    """ag_slots_out: per slot [max_slots][B], per auction [B], per participant [P][B]."""
+    _fields_ = [("struct_size", ctypes.c_uint64), ("winner", ctypes.c_void_p), ("price", ctypes.c_void_p),
+                ("second_price", ctypes.c_void_p), ("outcome", ctypes.c_void_p),
+                ("log_price", ctypes.c_void_p), ("num_filled", ctypes.c_void_p),
+                ("item", ctypes.c_void_p), ("bid", ctypes.c_void_p), ("est_ctr", ctypes.c_void_p),
+                ("true_ctr", ctypes.c_void_p), ("best_ev", ctypes.c_void_p),
+                ("gamma", ctypes.c_void_p), ("propensity", ctypes.c_void_p), ("won_slot", ctypes.c_void_p)]
 
 
 class AgLrtsSamples(_Sized):
@@ -174,6 +186,14 @@ def load(path=None):
                                                      ctypes.c_double, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp,
                                                      vp, vp, vp, vp, vp, vp, vp]),
         "ag_torch_normal_epochs": (ctypes.c_int, [vp, i64, i64, i32, vp]),
+        "ag_simulate_slots": (ctypes.c_int, [vp, i64, ctypes.POINTER(AgBatchIn), vp, vp,
+                                             ctypes.POINTER(AgSlotsOut), vp, vp]),
+        "ag_allocate_slots": (ctypes.c_int, [vp, vp, vp, i32, i64, vp, vp, vp, vp]),
+        "ag_replay_draw_slots": (ctypes.c_int, [ctypes.POINTER(AgPcg64State), i64, i32, i32, i32, ctypes.c_double,
+                                                i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "ag_replay_draw_population_slots": (ctypes.c_int, [ctypes.POINTER(AgPcg64State), vp, i64, i64, i32, i32, i32,
+                                                           ctypes.c_double, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp,
+                                                           vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "ag_bidder_rp_begin": (ctypes.c_int, [vp, ctypes.POINTER(AgShadingSamples), vp, vp, vp, vp, vp]),
         "ag_bidder_rp_epoch": (ctypes.c_int, [vp, i32, ctypes.POINTER(i64), vp, vp]),
         "ag_bidder_rp_run": (ctypes.c_int, [vp, vp, vp]),

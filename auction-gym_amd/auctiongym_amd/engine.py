@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import AgBatchIn, AgBatchOut, AgLrtsSamples, AgShadingSamples, AgShape
+from ._lib import AgBatchIn, AgBatchOut, AgLrtsSamples, AgShadingSamples, AgShape, AgSlotsOut
 from ._lib import check as _check
 
 COUNTERS = _lib.COUNTERS
@@ -34,6 +34,11 @@ def unpack_outputs(outputs):
         o["winner"] = (wo & 0x7fffffff).to(torch.int32)
         o["outcome"] = (wo >> 31).to(torch.uint8)
     return o
+
+
+# ag_slots_out (multi-slot rounds): per slot [max_slots][B], per auction [B], per participant [P][B]
+_SLOT_FIELDS = ("winner", "price", "second_price", "outcome", "log_price", "num_filled", "item", "bid",
+                "est_ctr", "true_ctr", "best_ev", "gamma", "propensity", "won_slot")
 
 
 def _batch_out(outputs):
@@ -63,7 +68,7 @@ class AuctionEngine:
     """Batched Auction.simulate_opportunity for N agents, P participants, K items, E dims."""
 
     def __init__(self, num_agents, num_participants, num_items, embedding_size,
-                 obs_embedding_size, mechanism, embedding_var=1.0, device=None, lib_path=None):
+                 obs_embedding_size, mechanism, embedding_var=1.0, device=None, lib_path=None, max_slots=1):
         require_gpu()
         self.L = _lib.load(lib_path)
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
@@ -72,7 +77,8 @@ class AuctionEngine:
         self.D = self.E + 1
         self.mechanism = int(mechanism)
         self.embedding_var = float(embedding_var)
-        shape = AgShape(self.N, self.P, self.K, self.E, self.OE, self.mechanism, 1, 0,
+        self.max_slots = int(max_slots)  # several slots: simulate_slots (simulate serves one)
+        shape = AgShape(self.N, self.P, self.K, self.E, self.OE, self.mechanism, self.max_slots, 0,
                         self.embedding_var)
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
@@ -334,6 +340,59 @@ class AuctionEngine:
         bo = _batch_out(outputs)
         self._check(self.L.ag_simulate(self._h, B, ctypes.byref(bi), ctypes.byref(bo),
                                  _ptr(counters), _stream()), "ag_simulate")
+
+    def alloc_slot_outputs(self, B, fields=None):
+        """Device output arrays (ag_slots_out) of B multi-slot auctions: winner, price,
+        second_price, outcome [max_slots][B]; log_price, num_filled [B]; the per-participant
+        arrays of alloc_outputs and won_slot [P][B]."""
+        if fields is None:
+            fields = [f for f in _SLOT_FIELDS if f not in ("gamma", "propensity") or getattr(self, "shading", False)]
+        d, P, S = self.device, self.P, self.max_slots
+        f64 = torch.float64
+        spec = {"winner": ((S, B), torch.int32), "price": ((S, B), f64), "second_price": ((S, B), f64),
+                "outcome": ((S, B), torch.uint8), "log_price": ((B,), f64), "num_filled": ((B,), torch.int32),
+                "item": ((P, B), torch.int32), "bid": ((P, B), f64), "est_ctr": ((P, B), f64),
+                "true_ctr": ((P, B), f64), "best_ev": ((P, B), f64), "gamma": ((P, B), f64),
+                "propensity": ((P, B), f64), "won_slot": ((P, B), torch.int8)}
+        return {k: torch.empty(spec[k][0], dtype=spec[k][1], device=d) for k in fields}
+
+    def simulate_slots(self, inputs, num_slots, u_slots, outputs, counters=None):
+        """B rounds with several slots (ag_simulate_slots): inputs as simulate (its "u" is not
+        read and may be absent), num_slots int32 [B] in 1..max_slots, u_slots float64 [rows][B]
+        with rows >= min(max_slots, P), row k the k-th double the round's binomial consumes."""
+        B = num_slots.shape[0]
+        for k, t in list(inputs.items()) + [("num_slots", num_slots), ("u_slots", u_slots)]:
+            if not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"input {k} must be a contiguous tensor on {self.device}")
+        if inputs["ctx"].shape != (self.E, B) or inputs["part"].shape != (self.P, B):
+            raise ValueError("inputs must be SoA: ctx [E][B], part [P][B]")
+        if (num_slots.dtype != torch.int32 or u_slots.dtype != torch.float64 or u_slots.dim() != 2
+                or u_slots.shape[1] != B or u_slots.shape[0] < min(self.max_slots, self.P)):
+            raise ValueError("num_slots must be int32 [B], u_slots float64 [min(max_slots, P)][B]")
+        bi = _batch_in(inputs)
+        so = AgSlotsOut(*[_ptr(outputs.get(f)).value for f in _SLOT_FIELDS])
+        self._check(self.L.ag_simulate_slots(self._h, B, ctypes.byref(bi), _ptr(num_slots), _ptr(u_slots),
+                                             ctypes.byref(so), _ptr(counters), _stream()), "ag_simulate_slots")
+
+    def allocate_slots(self, bids, num_slots=None, max_slots=None):
+        """Batched allocate(bids, num_slots) (ag_allocate_slots): bids float64 [P][B], num_slots
+        int32 [B] (None: max_slots everywhere) -> winner int32, price, second_price
+        [max_slots][B], padded with -1 / NaN beyond what the reference's allocate returns."""
+        if bids.dim() != 2 or bids.shape[0] != self.P or bids.dtype != torch.float64:
+            raise ValueError("bids must be a float64 [P][B] tensor")
+        S = self.max_slots if max_slots is None else int(max_slots)
+        bids = bids.contiguous()
+        B = bids.shape[1]
+        if num_slots is not None:
+            if num_slots.dtype != torch.int32 or num_slots.shape != (B,):
+                raise ValueError("num_slots must be an int32 [B] tensor")
+            num_slots = num_slots.contiguous()
+        w = torch.empty((S, B), dtype=torch.int32, device=self.device)
+        p = torch.empty((S, B), dtype=torch.float64, device=self.device)
+        s = torch.empty((S, B), dtype=torch.float64, device=self.device)
+        self._check(self.L.ag_allocate_slots(self._h, _ptr(bids), _ptr(num_slots), S, B, _ptr(w), _ptr(p), _ptr(s),
+                                             _stream()), "ag_allocate_slots")
+        return w, p, s
 
     def simulate_generated(self, seed, first_auction, outputs, counters=None):
         """Generate mode (ag_simulate_generated): B = outputs["winner"].shape[0] rounds whose

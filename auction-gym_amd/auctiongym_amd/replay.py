@@ -17,6 +17,11 @@ generator (src/Models.py:31). draw_round_population makes the same calls in the 
 
 (The one exception: numpy's binomial draws nothing when p == 0.0 exactly, i.e. when a
 winner's sigmoid underflows to 0, which needs items . ctx < -745.)
+
+With max_slots > 1 the round's n = integers(1, max_slots + 1) matters: allocate returns
+min(n, P) winners and binomial(1, CTRs[winners]) consumes one next_double per winner, in rank
+order (src/Auction.py:60-65). The *_slots functions keep n and draw those min(n, P) doubles;
+the functions above draw the word and one double, which is right for one slot only.
 """
 import numpy as np
 import torch
@@ -44,8 +49,50 @@ def draw_rounds(rng, B, num_agents, num_participants, embedding_size, embedding_
     return ctx, part, u
 
 
+def _draw_slot_uniforms(rng, n, num_participants, max_slots):
+    """The doubles rng.binomial(1, CTRs[winners]) consumes: min(n, P), NaN-padded to min(max_slots, P)."""
+    us = np.full(min(max_slots, num_participants), np.nan)
+    for k in range(min(n, num_participants)):
+        us[k] = rng.random()
+    return us
+
+
+def draw_round_slots(rng, num_agents, num_participants, embedding_size, embedding_var, max_slots):
+    """One multi-slot round of an OracleAllocator + TruthfulBidder population: ctx, part, the
+    round's slot count n and u_slots [min(max_slots, P)] (NaN where nothing is consumed)."""
+    n = int(rng.integers(1, max_slots + 1))
+    ctx = rng.normal(0, embedding_var, size=embedding_size)
+    part = rng.choice(num_agents, num_participants, replace=False)
+    return ctx, part, n, _draw_slot_uniforms(rng, n, num_participants, max_slots)
+
+
+def draw_rounds_slots(rng, B, num_agents, num_participants, embedding_size, embedding_var, max_slots):
+    """B rounds of draw_round_slots -> SoA host arrays ctx [E][B], part [P][B] int32, num_slots
+    [B] int32, u_slots [min(max_slots, P)][B]."""
+    ctx = np.empty((embedding_size, B))
+    part = np.empty((num_participants, B), np.int32)
+    ns = np.empty(B, np.int32)
+    us = np.empty((min(max_slots, num_participants), B))
+    for r in range(B):
+        ctx[:, r], part[:, r], ns[r], us[:, r] = draw_round_slots(rng, num_agents, num_participants,
+                                                                 embedding_size, embedding_var, max_slots)
+    return ctx, part, ns, us
+
+
 M128 = (1 << 128) - 1
 M64 = (1 << 64) - 1
+
+
+def draw_rounds_native_slots(rng, B, num_agents, num_participants, embedding_size, embedding_var, max_slots,
+                             shading=None):
+    """draw_rounds_native for multi-slot rounds (ag_replay_draw_slots): B rounds of
+    draw_round_slots (with `shading`, of draw_round_population's numpy-only draws too) in C, the
+    same numbers and generator state as the Python loop. Returns ctx [E][B], part [P][B], gamma_raw
+    [P][B] or None, num_slots [B] int32, u_slots [min(max_slots, P)][B] (NaN where nothing is
+    consumed)."""
+    ctx, part, _, g, ns, us = _native_draws(rng, B, num_agents, num_participants, embedding_size, embedding_var,
+                                            max_slots, shading, None, True)
+    return ctx, part, g, ns, us
 
 
 def draw_rounds_native(rng, B, num_agents, num_participants, embedding_size, embedding_var, max_slots=1,
@@ -56,6 +103,14 @@ def draw_rounds_native(rng, B, num_agents, num_participants, embedding_size, emb
     loop. rng must be a numpy Generator on PCG64. Returns SoA host arrays ctx [E][B], part
     [P][B] int32, u [B] and gamma_raw [P][B] (NaN where nothing is drawn; None without
     shading). `out` may supply the arrays (e.g. pinned host tensors' numpy views)."""
+    return _native_draws(rng, B, num_agents, num_participants, embedding_size, embedding_var, max_slots, shading,
+                         out, False)[:4]
+
+
+def _native_draws(rng, B, num_agents, num_participants, embedding_size, embedding_var, max_slots, shading, out, slots):
+    """The C call behind draw_rounds_native (slots False: ag_replay_draw) and draw_rounds_native_slots
+    (True: ag_replay_draw_slots). Always (ctx, part, u, gamma_raw, num_slots, u_slots); the last two
+    are None for one-slot draws."""
     import ctypes
 
     from . import _lib
@@ -82,14 +137,22 @@ def draw_rounds_native(rng, B, num_agents, num_participants, embedding_size, emb
             raise ValueError("replay arrays must be C-contiguous")
     ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
     L = _lib.load()
-    _lib.check(L.ag_replay_draw(ctypes.byref(c), B, N, P, E, float(embedding_var), int(max_slots), ptr(sh), ptr(pg),
-                                ptr(gs), ptr(ctx), ptr(part), ptr(g), ptr(u)), "ag_replay_draw", L)
+    ns = us = None
+    if slots:
+        ns = np.empty(B, np.int32)
+        us = np.empty((min(int(max_slots), P), B))
+        _lib.check(L.ag_replay_draw_slots(ctypes.byref(c), B, N, P, E, float(embedding_var), int(max_slots), ptr(sh),
+                                          ptr(pg), ptr(gs), ptr(ctx), ptr(part), ptr(g), ptr(u), ptr(ns), ptr(us)),
+                   "ag_replay_draw_slots", L)
+    else:
+        _lib.check(L.ag_replay_draw(ctypes.byref(c), B, N, P, E, float(embedding_var), int(max_slots), ptr(sh),
+                                    ptr(pg), ptr(gs), ptr(ctx), ptr(part), ptr(g), ptr(u)), "ag_replay_draw", L)
     st["state"]["state"] = (int(c.state_hi) << 64) | int(c.state_lo)
     st["state"]["inc"] = (int(c.inc_hi) << 64) | int(c.inc_lo)
     st["has_uint32"] = int(c.has_uint32)
     st["uinteger"] = int(c.uinteger)
     bg.state = st
-    return ctx, part, u, g
+    return ctx, part, u, g, ns, us
 
 
 def _pcg_in(rng):
@@ -109,6 +172,14 @@ def _pcg_out(rng, st, c):
     rng.bit_generator.state = st
 
 
+def draw_rounds_native_population_slots(rng, B, num_agents, num_participants, embedding_size, embedding_var,
+                                        shading, ts_models, max_slots, policy=None, search=None, kdo_max=None):
+    """draw_rounds_native_population for multi-slot rounds (ag_replay_draw_population_slots):
+    its returns, then num_slots [B] int32 and u_slots [min(max_slots, P)][B]; u is row 0."""
+    return _native_population_draws(rng, B, num_agents, num_participants, embedding_size, embedding_var,
+                                    shading, ts_models, max_slots, policy, search, kdo_max, True)
+
+
 def draw_rounds_native_population(rng, B, num_agents, num_participants, embedding_size, embedding_var,
                                   shading, ts_models, max_slots=1, policy=None, search=None, kdo_max=None):
     """B rounds of draw_round_population in C (ag_replay_draw_population): numpy's draws and
@@ -119,6 +190,16 @@ def draw_rounds_native_population(rng, B, num_agents, num_participants, embeddin
     or None, u [B], ts_noise in the kernel's tile layout [P][ceil(B/64)][K*Do][64] or None,
     policy_eps [P][B] float32 or None, gamma_grid [P][128][B] or None. kdo_max: the noise rows'
     width K*Do (default: the largest model's)."""
+    return _native_population_draws(rng, B, num_agents, num_participants, embedding_size, embedding_var,
+                                    shading, ts_models, max_slots, policy, search, kdo_max, False)[:7]
+
+
+def _native_population_draws(rng, B, num_agents, num_participants, embedding_size, embedding_var, shading, ts_models,
+                             max_slots, policy, search, kdo_max, slots):
+    """The C call behind draw_rounds_native_population (slots False: ag_replay_draw_population) and
+    draw_rounds_native_population_slots (True: ag_replay_draw_population_slots). Always (ctx, part,
+    gamma_raw, u, ts_noise, policy_eps, gamma_grid, num_slots, u_slots); the last two are None for
+    one-slot draws."""
     import ctypes
 
     from . import _lib
@@ -155,14 +236,20 @@ def draw_rounds_native_population(rng, B, num_agents, num_participants, embeddin
         blob = torch.get_rng_state().numpy().copy()
     ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
     L = _lib.load()
-    _lib.check(L.ag_replay_draw_population(ctypes.byref(c), ptr(blob), 0 if blob is None else blob.size, B, N, P, E,
-                                           float(embedding_var), int(max_slots), ptr(sh), ptr(pg), ptr(gs), ptr(ts),
-                                           ptr(std), KDo, ptr(kdo), ptr(pol), ptr(sea), ptr(ctx), ptr(part), ptr(g), ptr(u),
-                                           ptr(noise), ptr(eps), ptr(grid)), "ag_replay_draw_population", L)
+    args = (ctypes.byref(c), ptr(blob), 0 if blob is None else blob.size, B, N, P, E, float(embedding_var),
+            int(max_slots), ptr(sh), ptr(pg), ptr(gs), ptr(ts), ptr(std), KDo, ptr(kdo), ptr(pol), ptr(sea), ptr(ctx),
+            ptr(part), ptr(g), ptr(u), ptr(noise), ptr(eps), ptr(grid))
+    ns = us = None
+    if slots:
+        ns = np.empty(B, np.int32)
+        us = np.empty((min(int(max_slots), P), B))
+        _lib.check(L.ag_replay_draw_population_slots(*args, ptr(ns), ptr(us)), "ag_replay_draw_population_slots", L)
+    else:
+        _lib.check(L.ag_replay_draw_population(*args), "ag_replay_draw_population", L)
     _pcg_out(rng, st, c)
     if blob is not None:
         torch.set_rng_state(torch.from_numpy(blob))
-    return ctx, part, g, u, noise, eps, grid
+    return ctx, part, g, u, noise, eps, grid, ns, us
 
 
 def draw_round_population(rng, num_agents, num_participants, embedding_size, embedding_var,
@@ -177,7 +264,27 @@ def draw_round_population(rng, num_agents, num_participants, embedding_size, emb
     nothing is drawn), u, ts_noise [P][K*Do] float32 or None, policy_eps [P] float32 (0
     where nothing is drawn) or None, gamma_grid [P][128] (0 where nothing is drawn) or
     None."""
-    rng.integers(1, max_slots + 1)
+    _, ctx, part, gamma_raw, noise, eps, grid = _round_population_draws(
+        rng, num_agents, num_participants, embedding_size, embedding_var, shading, ts_models, max_slots, policy,
+        search, kdo_max)
+    return ctx, part, gamma_raw, rng.random(), noise, eps, grid
+
+
+def draw_round_population_slots(rng, num_agents, num_participants, embedding_size, embedding_var,
+                                shading, ts_models, max_slots, policy=None, search=None, kdo_max=None):
+    """draw_round_population for a multi-slot round: (ctx, part, gamma_raw, u_slots [min(max_slots,
+    P)] (NaN where nothing is consumed), ts_noise, policy_eps, gamma_grid, the round's slot count n)."""
+    n, ctx, part, gamma_raw, noise, eps, grid = _round_population_draws(
+        rng, num_agents, num_participants, embedding_size, embedding_var, shading, ts_models, max_slots, policy,
+        search, kdo_max)
+    return ctx, part, gamma_raw, _draw_slot_uniforms(rng, n, num_participants, max_slots), noise, eps, grid, n
+
+
+def _round_population_draws(rng, num_agents, num_participants, embedding_size, embedding_var, shading, ts_models,
+                            max_slots, policy, search, kdo_max):
+    """A round's draws up to the participants' (everything before the clicks): (n, ctx, part,
+    gamma_raw, ts_noise, policy_eps, gamma_grid)."""
+    n = int(rng.integers(1, max_slots + 1))
     ctx = rng.normal(0, embedding_var, size=embedding_size)
     part = rng.choice(num_agents, num_participants, replace=False)
     gamma_raw = np.full(num_participants, np.nan)
@@ -206,5 +313,4 @@ def draw_round_population(rng, num_agents, num_participants, embedding_size, emb
         sh = shading[a]
         if sh is not None:
             gamma_raw[s] = rng.normal(sh[0], sh[1])
-    u = rng.random()
-    return ctx, part, gamma_raw, u, noise, eps, grid
+    return n, ctx, part, gamma_raw, noise, eps, grid

@@ -152,6 +152,7 @@ struct ag_ctx {
   int32_t sim_kernel = AG_SIM_KERNEL_AUTO;  // AG_OPT_SIMULATE_KERNEL
   int32_t grid_per_cu = 0;                  // AG_OPT_SIM_BLOCKS_PER_CU (0: as many as fit)
   int32_t block_threads = 0;                // AG_OPT_SIM_BLOCK_THREADS (0: auto)
+  int32_t resident_slots[3][8] = {};        // resident blocks of the multi-slot builds [SM 2, 4, 8][general][screened][counters]
   int32_t resident_ora[8] = {};             // resident blocks of k_oracle [specialised][generate][counters]
   // general populations (anything beyond OracleAllocator + TruthfulBidder)
   bool general = false, has_lrts = false, has_shading = false, lrts_loaded = false;
@@ -177,6 +178,15 @@ struct ag_ctx {
 void ag_lrts_release(ag_ctx *c);
 // Frees the DoublyRobustBidder workspace (ag_dr.hip).
 void ag_dr_release(ag_ctx *c);
+
+// One slot per auction only (ag_simulate, ag_simulate_generated, the record collectors): a
+// context created for several slots is sent to ag_simulate_slots.
+inline int ag_one_slot_only(const ag_ctx *c, const char *who) {
+  if (c && c->shape.num_slots > 1)
+    return ag_set_error(AG_ERR_UNSUPPORTED, "%s: the context has num_slots = %d; rounds with several slots run "
+                        "through ag_simulate_slots", who, c->shape.num_slots);
+  return AG_OK;
+}
 
 struct AgDeviceGuard {
   int prev = -1;

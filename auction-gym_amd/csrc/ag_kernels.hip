@@ -493,8 +493,20 @@ int simulate_oracle(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch_
 
 // k_simulate over a batch (replay / HBM-resident inputs, or generate mode: gen, every input drawn
 // in the kernel from (seed, first + auction index) as ag_generate + ag_generate_noise draw them)
+// sl: multi-slot rounds (ag_simulate_slots) -- the SLOTS build holding the context's max_slots,
+// 256 lanes, the whole population kind by kind at run time (kGenAll) or Oracle + Truthful
+SimKernel pick_slots(int sm, int D, bool prune, int general) {
+  switch (sm) {
+    case 2: return pick_slots_for<2>(D, prune, general);
+    case 4: return pick_slots_for<4>(D, prune, general);
+    case 8: return pick_slots_for<8>(D, prune, general);
+    default: return nullptr;
+  }
+}
+int slots_build(int max_slots) { return max_slots <= 2 ? 2 : (max_slots <= 4 ? 4 : 8); }
+
 int simulate_general(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch_out *out, int64_t *counters_fx,
-                     hipStream_t st, bool gen, uint64_t seed, uint64_t first) {
+                     hipStream_t st, bool gen, uint64_t seed, uint64_t first, const SlotsIo *sl = nullptr) {
   const ag_shape &s = c->shape;
   const int nc = s.num_agents * kC;
   const int D = c->D;
@@ -527,6 +539,7 @@ int simulate_general(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch
   prm.seed = seed;
   prm.first = first;
   prm.scale = s.embedding_var;
+  prm.sl = sl ? *sl : SlotsIo{};
   // (round 4 retired k_pop, the dedicated shipped-shape population kernel: k_simulate was as
   // fast or faster on every line, P = 8 included once its slots stream -- configs_1 at P = 8
   // 0.665 against 0.680 ms, profiles/r04k_ab_c1p8.log; at P = 2 on every line,
@@ -540,18 +553,24 @@ int simulate_general(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch
   // image among 16 waves. Same results (the counters are exact sums).
   int bt = c->block_threads;
   if (bt == 0) bt = (c->general && prune && lds > 40 * 1024) ? kLargeThreads : kThreads;
+  if (sl) bt = kThreads;
   // AG_OPT_SIM_GENERAL_MODE 0 (auto): TruthfulBidder-only populations take the build
   // without the bid-shading code (kGenTruthful); 1: always the full general build
-  const int gmode = !c->general ? kGenOracle : (c->has_shading || c->gen_mode_all) ? kGenAll : kGenTruthful;
+  const int gmode = !c->general ? kGenOracle : (c->has_shading || c->gen_mode_all || sl) ? kGenAll : kGenTruthful;
   // the shipped shape (E = 5, LR-TS width OE + 1 = 5 in the layout) has builds with the LR-TS
   // width compile-time (k_simulate's DOS); AG_OPT_SIM_SHIPPED_SHAPE 0 turns them off (A/B)
-  const int ship = (c->general && c->ship_shape && D == 6 && prm.lds.ts_do == kShipDo) ? kGenShip : 0;
+  const int ship = (!sl && c->general && c->ship_shape && D == 6 && prm.lds.ts_do == kShipDo) ? kGenShip : 0;
   // the full mix at P >= 3 in the large-image case: the streamed 768-lane build (shipped shape)
   if (bt == kLargeThreads && c->block_threads == 0 && gmode == kGenAll && ship && s.num_participants >= AG_STREAM_MIN_P &&
       s.num_participants <= kMaxP)
     bt = kMidThreads;
   const int genb = gen ? kGenGen : 0;  // generate mode: the shipped shape's GEN builds
-  SimKernel k = pick_kernel(s.num_participants, D, prune, gmode | ship | genb, bt);
+  const int sm = sl ? slots_build(sl->max_slots) : 0;
+  SimKernel k = sl ? pick_slots(sm, D, prune, gmode)
+                   : pick_kernel(s.num_participants, D, prune, gmode | ship | genb, bt);
+  if (sl && !k)
+    return ag_set_error(AG_ERR_UNSUPPORTED, "ag_simulate_slots: supports E+1 in 2..8 (P=%d D=%d)",
+                        s.num_participants, D);
   if (!k && bt == kMidThreads) {
     bt = kLargeThreads;
     k = pick_kernel(s.num_participants, D, prune, gmode | ship | genb, bt);
@@ -581,7 +600,9 @@ int simulate_general(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch
   }
   // Persistent grid: exactly the blocks the device keeps resident (no partial last round),
   // each striding over bt-auction tiles.
-  int &res = c->resident[(gen ? 128 : 0) + (bt == kMidThreads ? 64 : 0) + (ship ? 32 : 0) +
+  int &res = sl ? c->resident_slots[sm == 2 ? 0 : (sm == 4 ? 1 : 2)][(c->general ? 4 : 0) + (prune ? 2 : 0) +
+                                                                    (prm.want_counters ? 1 : 0)]
+                : c->resident[(gen ? 128 : 0) + (bt == kMidThreads ? 64 : 0) + (ship ? 32 : 0) +
                          (gmode == kGenTruthful ? 16 : 0) + (bt == kThreads ? 0 : 8) + (c->general ? 4 : 0) +
                          (prune ? 2 : 0) + (prm.want_counters ? 1 : 0)];
   if (res == 0) {  // first launch of this build: the kernel's static LDS (AG_TS_DMA's noise rings) on top
@@ -662,8 +683,11 @@ int ag_create(int32_t device, const ag_shape *s, ag_ctx **out) {
                      s->num_participants, s->num_agents);
   if (s->mechanism != AG_FIRST_PRICE && s->mechanism != AG_SECOND_PRICE)
     return ag_set_error(AG_ERR_INVALID, "ag_create: unknown mechanism %d", s->mechanism);
-  if (s->num_slots != 1)
-    return ag_set_error(AG_ERR_UNSUPPORTED, "ag_create: num_slots must be 1 (src/main.py:37)");
+  if (s->num_slots < 1)
+    return ag_set_error(AG_ERR_INVALID, "ag_create: num_slots must be >= 1 (num_slots=%d)", s->num_slots);
+  if (s->num_slots > AG_MAX_SLOTS)
+    return ag_set_error(AG_ERR_UNSUPPORTED, "ag_create: num_slots = %d: at most AG_MAX_SLOTS = %d slots are built",
+                        s->num_slots, AG_MAX_SLOTS);
   const int D = s->embedding_size + 1;
   if (s->num_participants > 4096)
     return ag_set_error(AG_ERR_UNSUPPORTED, "ag_create: P=%d > 4096", s->num_participants);
@@ -946,6 +970,7 @@ int ag_simulate(ag_ctx *c, int64_t B, const ag_batch_in *in, ag_batch_out *out_a
   ag_batch_out outv;
   AG_READ_OUT(out_arg, outv, "ag_simulate");
   const ag_batch_out *out = &outv;
+  if (int rc = ag_one_slot_only(c, "ag_simulate")) return rc;
   if (!c->can_simulate)
     return ag_set_error(AG_ERR_UNSUPPORTED,
                      "ag_simulate: supports E+1 in {2..9,11,13,16} (E+1 <= 8 when P > %d) and a catalogue "
@@ -983,12 +1008,77 @@ int ag_simulate(ag_ctx *c, int64_t B, const ag_batch_in *in, ag_batch_out *out_a
 }
 
 
+int ag_simulate_slots(ag_ctx *c, int64_t B, const ag_batch_in *in, const int32_t *num_slots, const double *u_slots,
+                      ag_slots_out *out, int64_t *counters_fx, void *stream) {
+  const char *who = "ag_simulate_slots";
+  if (!c || !in || !out) return ag_set_error(AG_ERR_INVALID, "%s: null argument", who);
+  AG_CHECK_STRUCT(in, who, "ag_batch_in");
+  AG_CHECK_STRUCT(out, who, "ag_slots_out");
+  const ag_shape &s = c->shape;
+  if (c->D > 8 || !c->can_simulate)
+    return ag_set_error(AG_ERR_UNSUPPORTED, "%s: supports E+1 in 2..8 and a catalogue that fits LDS (P=%d, D=%d, "
+                        "N=%d, K=%d)", who, s.num_participants, c->D, s.num_agents, s.num_items);
+  if (!c->catalog) return ag_set_error(AG_ERR_STATE, "%s: ag_load_catalog not called", who);
+  if (B < 0) return ag_set_error(AG_ERR_INVALID, "%s: B < 0", who);
+  if (B == 0) return AG_OK;
+  if (!in->ctx || !in->part || !num_slots || !u_slots)
+    return ag_set_error(AG_ERR_INVALID, "%s: null input array (ctx, part, num_slots, u_slots)", who);
+  if (B * std::max(s.num_participants, s.num_slots) > INT32_MAX)
+    return ag_set_error(AG_ERR_UNSUPPORTED, "%s: B * max(P, max_slots) must be < 2^31 (32-bit SoA indexing); "
+                        "split the batch", who);
+  if (c->has_lrts && !c->lrts_loaded) return ag_set_error(AG_ERR_STATE, "%s: LR-TS agents need ag_load_lrts", who);
+  if (c->has_lrts && c->ts_sample && !in->ts_noise)
+    return ag_set_error(AG_ERR_INVALID, "%s: Thompson sampling needs ts_noise", who);
+  if (c->has_shading && !in->gamma_raw) return ag_set_error(AG_ERR_INVALID, "%s: shading bidders need gamma_raw", who);
+  if (c->dr_any_init && !in->policy_eps)
+    return ag_set_error(AG_ERR_INVALID, "%s: learning bidders with a fitted policy need policy_eps", who);
+  if (c->vl_any_search && !in->gamma_grid)
+    return ag_set_error(AG_ERR_INVALID, "%s: ValueLearningBidders bidding by search need gamma_grid", who);
+  AgDeviceGuard g(c->device);
+  ag_batch_out po{};  // the per-participant arrays go through the kernel's ag_batch_out
+  po.struct_size = sizeof(ag_batch_out);
+  po.item = out->item;
+  po.bid = out->bid;
+  po.est_ctr = out->est_ctr;
+  po.true_ctr = out->true_ctr;
+  po.best_ev = out->best_ev;
+  po.gamma = out->gamma;
+  po.propensity = out->propensity;
+  const SlotsIo sl{num_slots, u_slots, s.num_slots, out->winner, out->price, out->second_price, out->outcome,
+                   out->log_price, out->num_filled, out->won_slot};
+  return simulate_general(c, B, in, &po, counters_fx, (hipStream_t)stream, false, 0, 0, &sl);
+}
+
+int ag_allocate_slots(ag_ctx *c, const double *bids, const int32_t *num_slots, int32_t max_slots, int64_t B,
+                      int32_t *winner, double *price, double *second_price, void *stream) {
+  if (!c || (!bids && B > 0)) return ag_set_error(AG_ERR_INVALID, "ag_allocate_slots: null argument");
+  if (B < 0) return ag_set_error(AG_ERR_INVALID, "ag_allocate_slots: B < 0");
+  if (max_slots < 1 || max_slots > AG_MAX_SLOTS)
+    return ag_set_error(AG_ERR_INVALID, "ag_allocate_slots: max_slots must be in 1..%d (max_slots=%d)", AG_MAX_SLOTS,
+                        max_slots);
+  const int P = c->shape.num_participants;
+  if (P > 64) return ag_set_error(AG_ERR_UNSUPPORTED, "ag_allocate_slots: P = %d > 64", P);
+  if (B == 0) return AG_OK;
+  AgDeviceGuard g(c->device);
+  hipStream_t st = (hipStream_t)stream;
+  const int mech = c->shape.mechanism;
+  hipError_t e;
+  switch (slots_build(max_slots)) {
+    case 2: e = launch_allocate_slots_for<2>(bids, num_slots, max_slots, B, P, mech, winner, price, second_price, st); break;
+    case 4: e = launch_allocate_slots_for<4>(bids, num_slots, max_slots, B, P, mech, winner, price, second_price, st); break;
+    default: e = launch_allocate_slots_for<8>(bids, num_slots, max_slots, B, P, mech, winner, price, second_price, st);
+  }
+  AG_HIP(e);
+  return AG_OK;
+}
+
 int ag_simulate_generated(ag_ctx *c, uint64_t seed, uint64_t first, int64_t B, ag_batch_out *out_arg,
                           int64_t *counters_fx, void *stream) {
   if (!c || !out_arg) return ag_set_error(AG_ERR_INVALID, "ag_simulate_generated: null argument");
   ag_batch_out outv;
   AG_READ_OUT(out_arg, outv, "ag_simulate_generated");
   const ag_batch_out *out = &outv;
+  if (int rc = ag_one_slot_only(c, "ag_simulate_generated")) return rc;
   if (!c->catalog) return ag_set_error(AG_ERR_STATE, "ag_simulate_generated: ag_load_catalog not called");
   if (B < 0) return ag_set_error(AG_ERR_INVALID, "ag_simulate_generated: B < 0");
   if (B == 0) return AG_OK;

@@ -636,6 +636,7 @@ extern "C" {
 
 int ag_lrts_collect(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch_out *out_arg,
                     const ag_lrts_samples *s, void *stream) {
+  if (int rc = ag_one_slot_only(c, "ag_lrts_collect")) return rc;
   if (int rc = check_store(c, s, "ag_lrts_collect")) return rc;
   if (!in || !out_arg) return ag_set_error(AG_ERR_INVALID, "ag_lrts_collect: null argument");
   AG_CHECK_STRUCT(in, "ag_lrts_collect", "ag_batch_in");

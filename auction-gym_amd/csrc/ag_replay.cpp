@@ -361,18 +361,64 @@ void parallel_for(int64_t n, F fn) {
   for (auto &t : th) t.join();
 }
 
-}  // namespace
+// The round's slots word and the doubles rng.binomial(1, CTRs[winners]) consumes, shared by the
+// four draw functions. One slot per auction (slots = false: ag_replay_draw, ag_replay_draw_population):
+// the word is drawn and dropped, one double goes to u. Several (the *_slots functions): the word
+// is kept in num_slots, min(num_slots, P) doubles go to the rows of u_slots [min(max_slots, P)][B]
+// (NaN below), the first to u as well when u is given.
+struct SlotDraws {
+  bool slots;
+  int32_t max_slots, P;
+  int64_t B;
+  double *u;
+  int32_t *num_slots;
+  double *u_slots;
+  int64_t n = 1;  // this round's slots
+  // rng.integers(1, max_slots + 1) (src/Auction.py:30); nothing drawn for one slot
+  void draw_word(bitgen_t *bg, int64_t r) {
+    n = 1;
+    if (max_slots > 1) {
+      uint64_t w;
+      random_bounded_uint64_fill(bg, 1, (uint64_t)(max_slots - 1), 1, false, &w);
+      n = (int64_t)w;
+    }
+    if (slots) num_slots[r] = (int32_t)n;
+  }
+  // rng.binomial(1, p) consumes one next_double per element of p (src/Auction.py:65)
+  void draw_uniforms(Pcg64 *st, int64_t r) {
+    if (!slots) {
+      u[r] = pcg_next_double(st);
+      return;
+    }
+    const int rows = max_slots < P ? max_slots : P;
+    const int64_t take = n < P ? n : P;
+    for (int k = 0; k < rows; ++k) u_slots[(int64_t)k * B + r] = k < take ? pcg_next_double(st) : (double)NAN;
+    if (u) u[r] = u_slots[r];
+  }
+};
 
-extern "C" int ag_replay_draw(ag_pcg64_state *rng, int64_t B, int32_t N, int32_t P, int32_t E, double embedding_var,
-                              int32_t max_slots, const uint8_t *shading, const double *prev_gamma,
-                              const double *gamma_sigma, double *ctx, int32_t *part, double *gamma_raw, double *u) {
-  if (!rng || !ctx || !part || !u) return ag_set_error(AG_ERR_INVALID, "ag_replay_draw: null argument");
-  if (int rc = ag_check_struct(rng, "ag_replay_draw", "ag_pcg64_state")) return rc;
+int check_slot_args(const char *who, bool slots, const double *u, const int32_t *num_slots, const double *u_slots,
+                    int32_t max_slots) {
+  if (!slots) return u ? AG_OK : ag_set_error(AG_ERR_INVALID, "%s: null argument", who);
+  if (!num_slots || !u_slots) return ag_set_error(AG_ERR_INVALID, "%s: null num_slots / u_slots", who);
+  if (max_slots > AG_MAX_SLOTS)
+    return ag_set_error(AG_ERR_UNSUPPORTED, "%s: max_slots = %d > AG_MAX_SLOTS = %d", who, max_slots, AG_MAX_SLOTS);
+  return AG_OK;
+}
+
+int replay_draw(const char *who, bool slots, ag_pcg64_state *rng, int64_t B, int32_t N, int32_t P, int32_t E,
+                double embedding_var, int32_t max_slots, const uint8_t *shading, const double *prev_gamma,
+                const double *gamma_sigma, double *ctx, int32_t *part, double *gamma_raw, double *u,
+                int32_t *num_slots, double *u_slots) {
+  if (!rng || !ctx || !part) return ag_set_error(AG_ERR_INVALID, "%s: null argument", who);
+  if (int rc = check_slot_args(who, slots, u, num_slots, u_slots, max_slots)) return rc;
+  if (int rc = ag_check_struct(rng, who, "ag_pcg64_state")) return rc;
   if (B < 0 || N < 1 || P < 1 || E < 0 || max_slots < 1)
-    return ag_set_error(AG_ERR_INVALID, "ag_replay_draw: bad sizes");
+    return ag_set_error(AG_ERR_INVALID, "%s: bad sizes", who);
   if (P > N) return ag_set_error(AG_ERR_INVALID, "Cannot take a larger sample than population when replace is False");
   if (shading && (!prev_gamma || !gamma_sigma || !gamma_raw))
-    return ag_set_error(AG_ERR_INVALID, "ag_replay_draw: shading needs prev_gamma, gamma_sigma and gamma_raw");
+    return ag_set_error(AG_ERR_INVALID, "%s: shading needs prev_gamma, gamma_sigma and gamma_raw", who);
+  SlotDraws sd{slots, max_slots, P, B, u, num_slots, u_slots};
   Pcg64 st;
   st.state = ((unsigned __int128)rng->state_hi << 64) | rng->state_lo;
   st.inc = ((unsigned __int128)rng->inc_hi << 64) | rng->inc_lo;
@@ -382,10 +428,7 @@ extern "C" int ag_replay_draw(ag_pcg64_state *rng, int64_t B, int32_t N, int32_t
   std::vector<int64_t> sample((size_t)P), arange;
   std::vector<uint64_t> hash_set;
   for (int64_t r = 0; r < B; ++r) {
-    if (max_slots > 1) {  // rng.integers(1, max_slots + 1) (src/Auction.py:30); nothing drawn for 1 slot
-      uint64_t slots;
-      random_bounded_uint64_fill(&bg, 1, (uint64_t)(max_slots - 1), 1, false, &slots);
-    }
+    sd.draw_word(&bg, r);
     for (int e = 0; e < E; ++e) ctx[(int64_t)e * B + r] = random_normal(&bg, 0.0, embedding_var);  // :33
     choice_no_replace(&bg, N, P, sample.data(), arange, hash_set);                                  // :42
     for (int s = 0; s < P; ++s) {
@@ -396,7 +439,7 @@ extern "C" int ag_replay_draw(ag_pcg64_state *rng, int64_t B, int32_t N, int32_t
             (shading && shading[a]) ? random_normal(&bg, prev_gamma[a], gamma_sigma[a]) : (double)NAN;
       }
     }
-    u[r] = pcg_next_double(&st);  // rng.binomial(1, p) consumes one next_double (:65)
+    sd.draw_uniforms(&st, r);
   }
   rng->state_hi = (uint64_t)(st.state >> 64);
   rng->state_lo = (uint64_t)st.state;
@@ -407,19 +450,36 @@ extern "C" int ag_replay_draw(ag_pcg64_state *rng, int64_t B, int32_t N, int32_t
   return AG_OK;
 }
 
+}  // namespace
+
+extern "C" int ag_replay_draw(ag_pcg64_state *rng, int64_t B, int32_t N, int32_t P, int32_t E, double embedding_var,
+                              int32_t max_slots, const uint8_t *shading, const double *prev_gamma,
+                              const double *gamma_sigma, double *ctx, int32_t *part, double *gamma_raw, double *u) {
+  return replay_draw("ag_replay_draw", false, rng, B, N, P, E, embedding_var, max_slots, shading, prev_gamma,
+                     gamma_sigma, ctx, part, gamma_raw, u, nullptr, nullptr);
+}
+
+extern "C" int ag_replay_draw_slots(ag_pcg64_state *rng, int64_t B, int32_t N, int32_t P, int32_t E,
+                                    double embedding_var, int32_t max_slots, const uint8_t *shading,
+                                    const double *prev_gamma, const double *gamma_sigma, double *ctx, int32_t *part,
+                                    double *gamma_raw, double *u, int32_t *num_slots, double *u_slots) {
+  return replay_draw("ag_replay_draw_slots", true, rng, B, N, P, E, embedding_var, max_slots, shading, prev_gamma,
+                     gamma_sigma, ctx, part, gamma_raw, u, num_slots, u_slots);
+}
+
 // the Box-Muller block of torch's float normal kernel (host checks only: tests/test_host.py)
 extern "C" void ag_torch_normal_block16(float *d) { normal_block16(d); }
 
-extern "C" int ag_replay_draw_population(ag_pcg64_state *rng, uint8_t *torch_state, int64_t torch_state_bytes,
-                                         int64_t B, int32_t N, int32_t P, int32_t E, double embedding_var,
-                                         int32_t max_slots, const uint8_t *shading, const double *prev_gamma,
-                                         const double *gamma_sigma, const uint8_t *ts, const float *ts_std,
-                                         int32_t KDo, const int32_t *ts_kdo, const uint8_t *policy,
-                                         const uint8_t *search, double *ctx,
-                                         int32_t *part, double *gamma_raw, double *u, float *ts_noise,
-                                         float *policy_eps, double *gamma_grid) {
-  const char *who = "ag_replay_draw_population";
-  if (!rng || !ctx || !part || !u) return ag_set_error(AG_ERR_INVALID, "%s: null argument", who);
+namespace {
+int replay_draw_population(const char *who, bool slots, ag_pcg64_state *rng, uint8_t *torch_state,
+                           int64_t torch_state_bytes, int64_t B, int32_t N, int32_t P, int32_t E,
+                           double embedding_var, int32_t max_slots, const uint8_t *shading, const double *prev_gamma,
+                           const double *gamma_sigma, const uint8_t *ts, const float *ts_std, int32_t KDo,
+                           const int32_t *ts_kdo, const uint8_t *policy, const uint8_t *search, double *ctx,
+                           int32_t *part, double *gamma_raw, double *u, float *ts_noise, float *policy_eps,
+                           double *gamma_grid, int32_t *num_slots, double *u_slots) {
+  if (!rng || !ctx || !part) return ag_set_error(AG_ERR_INVALID, "%s: null argument", who);
+  if (int rc = check_slot_args(who, slots, u, num_slots, u_slots, max_slots)) return rc;
   if (int rc = ag_check_struct(rng, who, "ag_pcg64_state")) return rc;
   if (B < 0 || B >= (int64_t)1 << 31 || N < 1 || P < 1 || E < 0 || max_slots < 1)
     return ag_set_error(AG_ERR_INVALID, "%s: bad sizes", who);
@@ -453,11 +513,9 @@ extern "C" int ag_replay_draw_population(ag_pcg64_state *rng, uint8_t *torch_sta
   const int NU = ts ? KDo + 16 : 0;  // >= normal_fill_uniforms(n) for every n <= KDo
   std::vector<float> tsu(ts ? (size_t)B * P * NU : 0);  // the Thompson draws' uniforms, [B][P][NU]
   double grid[128];
+  SlotDraws sd{slots, max_slots, P, B, u, num_slots, u_slots};
   for (int64_t r = 0; r < B; ++r) {
-    if (max_slots > 1) {  // rng.integers(1, max_slots + 1) (src/Auction.py:30)
-      uint64_t slots;
-      random_bounded_uint64_fill(&bg, 1, (uint64_t)(max_slots - 1), 1, false, &slots);
-    }
+    sd.draw_word(&bg, r);
     for (int e = 0; e < E; ++e) ctx[(int64_t)e * B + r] = random_normal(&bg, 0.0, embedding_var);  // :33
     choice_no_replace(&bg, N, P, sample.data(), arange, hash_set);                                  // :42
     for (int s = 0; s < P; ++s) {
@@ -482,7 +540,7 @@ extern "C" int ag_replay_draw_population(ag_pcg64_state *rng, uint8_t *torch_sta
       if (shading && shading[a])  // an uninitialised shading bidder's Gaussian gamma
         gamma_raw[(int64_t)s * B + r] = random_normal(&bg, prev_gamma[a], gamma_sigma[a]);
     }
-    u[r] = pcg_next_double(&st);  // rng.binomial(1, p) consumes one next_double (:65)
+    sd.draw_uniforms(&st, r);
   }
   if (ts)  // the Box-Muller transforms of the Thompson draws, rounds in parallel
     parallel_for(B, [&](int64_t r0, int64_t r1) {
@@ -506,6 +564,35 @@ extern "C" int ag_replay_draw_population(ag_pcg64_state *rng, uint8_t *torch_sta
   rng->uinteger = st.uinteger;
   if (torch_draws) torch_store(tr, torch_state);
   return AG_OK;
+}
+}  // namespace
+
+extern "C" int ag_replay_draw_population(ag_pcg64_state *rng, uint8_t *torch_state, int64_t torch_state_bytes,
+                                         int64_t B, int32_t N, int32_t P, int32_t E, double embedding_var,
+                                         int32_t max_slots, const uint8_t *shading, const double *prev_gamma,
+                                         const double *gamma_sigma, const uint8_t *ts, const float *ts_std,
+                                         int32_t KDo, const int32_t *ts_kdo, const uint8_t *policy,
+                                         const uint8_t *search, double *ctx,
+                                         int32_t *part, double *gamma_raw, double *u, float *ts_noise,
+                                         float *policy_eps, double *gamma_grid) {
+  return replay_draw_population("ag_replay_draw_population", false, rng, torch_state, torch_state_bytes, B, N, P, E,
+                                embedding_var, max_slots, shading, prev_gamma, gamma_sigma, ts, ts_std, KDo, ts_kdo,
+                                policy, search, ctx, part, gamma_raw, u, ts_noise, policy_eps, gamma_grid, nullptr,
+                                nullptr);
+}
+
+extern "C" int ag_replay_draw_population_slots(ag_pcg64_state *rng, uint8_t *torch_state, int64_t torch_state_bytes,
+                                               int64_t B, int32_t N, int32_t P, int32_t E, double embedding_var,
+                                               int32_t max_slots, const uint8_t *shading, const double *prev_gamma,
+                                               const double *gamma_sigma, const uint8_t *ts, const float *ts_std,
+                                               int32_t KDo, const int32_t *ts_kdo, const uint8_t *policy,
+                                               const uint8_t *search, double *ctx, int32_t *part, double *gamma_raw,
+                                               double *u, float *ts_noise, float *policy_eps, double *gamma_grid,
+                                               int32_t *num_slots, double *u_slots) {
+  return replay_draw_population("ag_replay_draw_population_slots", true, rng, torch_state, torch_state_bytes, B, N,
+                                P, E, embedding_var, max_slots, shading, prev_gamma, gamma_sigma, ts, ts_std, KDo,
+                                ts_kdo, policy, search, ctx, part, gamma_raw, u, ts_noise, policy_eps, gamma_grid,
+                                num_slots, u_slots);
 }
 
 // `epochs` x torch.empty(n).normal_() from torch's CPU generator (the rsample draws of the

@@ -241,6 +241,7 @@ extern "C" {
 
 int ag_shading_collect(ag_ctx *c, int64_t first, int64_t B, const ag_batch_in *in, const ag_batch_out *out_arg,
                        const ag_shading_samples *s, void *stream) {
+  if (int rc = ag_one_slot_only(c, "ag_shading_collect")) return rc;
   if (int rc = check_store(c, s, "ag_shading_collect")) return rc;
   if (!in || !out_arg) return ag_set_error(AG_ERR_INVALID, "ag_shading_collect: null argument");
   AG_CHECK_STRUCT(in, "ag_shading_collect", "ag_batch_in");

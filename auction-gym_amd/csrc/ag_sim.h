@@ -276,6 +276,62 @@ __host__ inline void add_policy_tasks(LdsLayout &L, int bt) {
   L.total = align16((int64_t)L.total + (int64_t)bt * 32);
 }
 
+// Multi-slot rounds (ag_simulate_slots; k_simulate's SLOTS builds): the per-auction slot counts
+// and per-slot uniforms in, the per-slot / per-auction outputs and each participant's rank out.
+struct SlotsIo {
+  const int32_t *num_slots;  // [B], 1..max_slots (clamped)
+  const double *u;           // [max_slots][B]: row k the k-th double rng.binomial consumes
+  int32_t max_slots;         // ag_shape.num_slots: rows of the per-slot outputs
+  int32_t *winner;           // [max_slots][B]
+  double *price, *second_price;
+  uint8_t *outcome;
+  double *log_price;         // [B]
+  int32_t *num_filled;       // [B]
+  int8_t *won_slot;          // [P][B]
+};
+
+// The lane's ranking of a multi-slot auction: the best SM + 1 bids so far in descending order,
+// each with its participant slot and (CTR = true) the true CTR of its item, in registers. A bid
+// takes a rank only from bids it strictly exceeds (ties -> the lower participant slot: a stable
+// descending order, the one-slot kernels' `b > m1` rule extended; the reference's np.argsort order
+// among exactly tied bids is not pinned beyond that). As in top2_step, participant 0's bid opens
+// the list whatever it is, and a later NaN (or -inf) bid exceeds nothing and is never ranked.
+// The insertion is one fully unrolled pass with compile-time indices (a runtime-indexed register
+// array would live in scratch): the new entry is carried down the list and swapped in at the
+// first entry it exceeds, every later entry then moving one rank down.
+template <int SM, bool CTR>
+struct TopList {
+  double bid[SM + 1];
+  double ctr[CTR ? SM + 1 : 1];
+  int slot[SM + 1];
+  __device__ __forceinline__ void init() {
+#pragma unroll
+    for (int j = 0; j <= SM; ++j) {
+      bid[j] = -INFINITY;
+      slot[j] = -1;
+      if constexpr (CTR) ctr[j] = 0.0;
+    }
+  }
+  __device__ __forceinline__ void insert(int s, double b, double c) {
+    bool moved = s == 0;  // the first participant: rank 0, whatever its bid
+#pragma unroll
+    for (int j = 0; j <= SM; ++j) {
+      moved = moved || b > bid[j];
+      const double tb = bid[j];
+      const int ts = slot[j];
+      bid[j] = moved ? b : tb;
+      slot[j] = moved ? s : ts;
+      b = moved ? tb : b;
+      s = moved ? ts : s;
+      if constexpr (CTR) {
+        const double tc = ctr[j];
+        ctr[j] = moved ? c : tc;
+        c = moved ? tc : c;
+      }
+    }
+  }
+};
+
 struct SimParams {
   int32_t B;              // auctions in the batch = SoA leading dimension (B * P < 2^31)
   int32_t lo, hi;         // the auctions [lo, hi) this launch resolves
@@ -301,6 +357,7 @@ struct SimParams {
   const float *tsq;       // [N][K][OE+1] LR-TS q (the Thompson noise's scale 1 / sqrtf(q))
   uint64_t seed, first;   // Philox key; global index of the batch's auction 0
   double scale;           // embedding_var (the contexts' scale)
+  SlotsIo sl;             // multi-slot rounds (read by the SLOTS builds only)
 };
 
 // Screening margin. The screen ranks items by t_k = (1 + 2^(z'_k)) / v_k = 1 / (exact
@@ -999,7 +1056,10 @@ __device__ __forceinline__ void resolve(const Lds &T, int K, int mech, const dou
 // auction's global index, the bits ag_generate + ag_generate_noise store (contexts,
 // participants, uniform: gen_auction; Thompson noise, rsample and shading draws: resolve_slot);
 // only the outputs touch HBM. Shipped-shape builds (DOS > 0) only.
-template <int P, int D, bool PRUNE, int GENERAL, int BT = kThreads, int DOS = 0, bool GEN = false>
+// SLOTS: 0, or the multi-slot build (ag_simulate_slots) for up to SLOTS slots per auction: a
+// branch beside the runtime-P one (P == 0), sharing its prologue, resolve_slot and the exact
+// counters' accumulate and write-out.
+template <int P, int D, bool PRUNE, int GENERAL, int BT = kThreads, int DOS = 0, bool GEN = false, int SLOTS = 0>
 __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_MIN_WAVES : AG_TB_MIN_WAVES)
                                  : (GENERAL ? ((DOS && P > 0 && P <= 2) ? AG_GEN_DOS_MIN_WAVES : AG_GEN_MIN_WAVES)
                                             : 1)) void k_simulate(SimParams prm) {
@@ -1028,6 +1088,7 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
   constexpr bool kDma = AG_TS_DMA && GENERAL && DOS == 5 && !GEN && BT == kThreads && P >= 1 && P <= AG_TS_DMA_MAXP;
   __shared__ __attribute__((aligned(16))) float s_ring[kDma ? (BT / 64) * kTsDmaBufs * 5 * 64 : 1];
   static_assert(!GEN || (DOS > 0 && P > 0 && GENERAL), "generate mode: shipped-shape general builds");
+  static_assert(SLOTS == 0 || (P == 0 && !GEN && DOS == 0 && BT == kThreads), "multi-slot: the runtime-P form");
   unsigned long long *s_cnt = reinterpret_cast<unsigned long long *>(smem + L.cnt);
 
   const int tid = threadIdx.x;
@@ -1192,7 +1253,9 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
       if (won) {
         add_nz(kSlotGross, val * (double)oc);
         add_raw(kSlotPaid, price);
-        if (prm.mech == AG_FIRST_PRICE) add_nz(kSlotOverbid, lp - second);
+        // one slot: price - second_price is 0 under SecondPrice. Several: the logged price is the
+        // last filled slot's, so the term is nonzero (even negative) under either mechanism
+        if (SLOTS > 0 || prm.mech == AG_FIRST_PRICE) add_nz(kSlotOverbid, lp - second);
       } else {
         add_nz(kSlotUnderbid, (lp - bid) * (double)(lp < tv));
       }
@@ -1247,11 +1310,107 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
       atomicAdd(s_cnt + ((size_t)(kSlotCounts * N + a) * R + rep), won ? 0x100000001ull : 1ull);
     }
   };
+  // the runtime-P forms (P == 0, one slot or several): the lane's context loaded from HBM with its
+  // intercept, float copy and screening bound; a participant's outputs stored as it is resolved
+  auto load_context = [&](uint32_t i, double (&x)[kMaxD], float (&xf)[kMaxD], float &xabs) {
+    xabs = 1.0f;
+#pragma unroll
+    for (int e = 0; e < D - 1; ++e) {
+      x[e] = ldg(in.ctx + e * B + i);
+      xf[e] = (float)x[e];
+      xabs += fabsf(xf[e]);
+    }
+    x[D - 1] = 1.0;  // intercept (src/Auction.py:33)
+    xf[D - 1] = 1.0f;
+    xabs *= 1.001f;
+  };
+  auto store_participant = [&](uint32_t o, const SlotResult &q) {
+    if (out.item) stg(out.item + o, (int32_t)q.item);
+    if (out.bid) stg(out.bid + o, q.bid);
+    if (out.est_ctr) stg(out.est_ctr + o, q.est);
+    if (out.true_ctr) stg(out.true_ctr + o, q.ctr);
+    if (out.best_ev) stg(out.best_ev + o, q.bev);
+    if (out.gamma) stg(out.gamma + o, q.gamma);
+    if (out.propensity) stg(out.propensity + o, q.prop);
+  };
   for (uint32_t base = lo + blockIdx.x * BT; base < hi; base += stride) {
     const uint32_t i = base + tid;
     // generate mode: the auction's Philox counter (its global index) for the slots' draws
     const GenKey gk{(uint32_t)(prm.first + i), (uint32_t)((prm.first + i) >> 32), gk0, gk1};
     if (i >= hi) continue;
+    if constexpr (SLOTS > 0) {
+      // Several slots (src/Auction.py:30, :60-74): the participants resolved in a loop as in the
+      // runtime-P path below, their outputs stored as they come, the best SLOTS + 1 bids kept
+      // ranked in registers; then the per-slot outputs, and for the counters the participants
+      // resolved once more (the same arithmetic: the same values), each record counted with its
+      // own price, second price and click and the auction's logged price.
+      constexpr int SM = SLOTS;
+      const SlotsIo &sl = prm.sl;
+      const int Pn = prm.P;
+      double x[kMaxD];
+      float xf[kMaxD];
+      float xabs;
+      load_context(i, x, xf, xabs);
+      int n = ldg(sl.num_slots + i);
+      n = n < 1 ? 1 : (n > sl.max_slots ? sl.max_slots : n);
+      const int F = n < Pn - 1 ? n : Pn - 1;  // filled slots: zip stops at the second prices
+      TopList<SM, true> top;
+      top.init();
+      for (int s = 0; s < Pn; ++s) {
+        const uint32_t o = (uint32_t)s * B + i;
+        const int a = ldg(in.part + o);
+        const SlotResult q = resolve_slot<D, PRUNE, GENERAL>(T, K, x, xf, xabs, a, s, in, B, i, prm.ts_sample != 0);
+        store_participant(o, q);
+        top.insert(s, q.bid, q.ctr);
+      }
+      // slot k < F: its price, second price and click (the k-th consumed double)
+      double pk[SM], lp = NAN;
+      int ock[SM];
+#pragma unroll
+      for (int k = 0; k < SM; ++k) {
+        const bool filled = k < F;
+        pk[k] = prm.mech == AG_FIRST_PRICE ? top.bid[k] : top.bid[k + 1];
+        ock[k] = filled ? bernoulli(top.ctr[k], ldg(sl.u + (size_t)k * B + i)) : 0;
+        if (k == F - 1) lp = pk[k];
+        if (k < sl.max_slots) {
+          const size_t o = (size_t)k * B + i;
+          if (sl.winner) stg(sl.winner + o, filled ? (int32_t)top.slot[k] : (int32_t)-1);
+          if (sl.price) stg(sl.price + o, filled ? pk[k] : (double)NAN);
+          if (sl.second_price) stg(sl.second_price + o, filled ? top.bid[k + 1] : (double)NAN);
+          if (sl.outcome) stg(sl.outcome + o, (uint8_t)ock[k]);
+        }
+      }
+      if (sl.log_price) stg(sl.log_price + i, lp);
+      if (sl.num_filled) stg(sl.num_filled + i, (int32_t)(F < 0 ? 0 : F));
+      // the rank participant slot s won (-1: none), by compile-time indices
+      auto rank_of = [&](int s) {
+        int r = -1;
+#pragma unroll
+        for (int k = 0; k < SM; ++k) r = (k < F && top.slot[k] == s) ? k : r;
+        return r;
+      };
+      if (sl.won_slot)
+        for (int s = 0; s < Pn; ++s) stg(sl.won_slot + ((uint32_t)s * B + i), (int8_t)rank_of(s));
+      if (prm.want_counters) {
+        const double lpc = F > 0 ? lp : 0.0;  // nobody charged: the logged price stays 0
+        for (int s = 0; s < Pn; ++s) {
+          const int a = ldg(in.part + (uint32_t)s * B + i);
+          const SlotResult q =
+              resolve_slot<D, PRUNE, GENERAL>(T, K, x, xf, xabs, a, s, in, B, i, prm.ts_sample != 0);
+          const int r = rank_of(s);
+          double price = 0.0, second = 0.0;
+          int oc = 0;
+#pragma unroll
+          for (int k = 0; k < SM; ++k) {
+            price = r == k ? pk[k] : price;
+            second = r == k ? top.bid[k + 1] : second;
+            oc = r == k ? ock[k] : oc;
+          }
+          count_slot(a, r >= 0, lpc, price, second, q.bid, q.ctr, q.val, q.est, q.bev, oc);
+        }
+      }
+      continue;
+    }
     if constexpr (P == 0) {
       // more than kMaxP participants (runtime P): the slots are resolved in a loop, their
       // outputs written as they come; the counter terms need the winner and price, so the
@@ -1259,16 +1418,8 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
       const int Pn = prm.P;
       double x[kMaxD];
       float xf[kMaxD];
-      float xabs = 1.0f;
-#pragma unroll
-      for (int e = 0; e < D - 1; ++e) {
-        x[e] = ldg(in.ctx + e * B + i);
-        xf[e] = (float)x[e];
-        xabs += fabsf(xf[e]);
-      }
-      x[D - 1] = 1.0;  // intercept (src/Auction.py:33)
-      xf[D - 1] = 1.0f;
-      xabs *= 1.001f;
+      float xabs;
+      load_context(i, x, xf, xabs);
       const double u = ldg(in.u + i);
       double m1 = 0.0, m2 = -INFINITY, ctr_w = 0.0;
       int w = 0;
@@ -1276,13 +1427,7 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
         const uint32_t o = (uint32_t)s * B + i;
         const int a = ldg(in.part + o);
         const SlotResult q = resolve_slot<D, PRUNE, GENERAL>(T, K, x, xf, xabs, a, s, in, B, i, prm.ts_sample != 0);
-        if (out.item) stg(out.item + o, (int32_t)q.item);
-        if (out.bid) stg(out.bid + o, q.bid);
-        if (out.est_ctr) stg(out.est_ctr + o, q.est);
-        if (out.true_ctr) stg(out.true_ctr + o, q.ctr);
-        if (out.best_ev) stg(out.best_ev + o, q.bev);
-        if (out.gamma) stg(out.gamma + o, q.gamma);
-        if (out.propensity) stg(out.propensity + o, q.prop);
+        store_participant(o, q);
         top2_step(s, q.bid, m1, m2, w);
         if (w == s) ctr_w = q.ctr;  // the current leader's true CTR
       }
@@ -1670,6 +1815,23 @@ typedef void (*SimKernel)(SimParams);
 
 // Defined per participant count P in ag_sim_p.hip (one translation unit per P, compiled
 // in parallel): the k_simulate instantiation for (D, screened search, population, lanes).
+// The multi-slot builds, one translation unit per SM in {2, 4, 8} (ag_sim_slots.hip):
+// k_simulate<0, D, prune, general, 256 lanes, SLOTS = SM> for D = 2..8, general in {kGenOracle,
+// kGenAll} (nullptr otherwise), and the launch of k_allocate_slots<SM> (stream-ordered).
+template <int SM>
+SimKernel pick_slots_for(int D, bool prune, int general);
+template <int SM>
+hipError_t launch_allocate_slots_for(const double *bids, const int32_t *num_slots, int max_slots, int64_t B, int P,
+                                     int mech, int32_t *winner, double *price, double *second, hipStream_t st);
+#define AG_SLOTS_BUILD(SM)                                                                                       \
+  template <> SimKernel pick_slots_for<SM>(int, bool, int);                                                      \
+  template <> hipError_t launch_allocate_slots_for<SM>(const double *, const int32_t *, int, int64_t, int, int, \
+                                                       int32_t *, double *, double *, hipStream_t);
+AG_SLOTS_BUILD(2)
+AG_SLOTS_BUILD(4)
+AG_SLOTS_BUILD(8)
+#undef AG_SLOTS_BUILD
+
 template <int P>
 SimKernel pick_kernel_for(int D, bool prune, int general, int bt);
 template <> SimKernel pick_kernel_for<0>(int, bool, int, int);

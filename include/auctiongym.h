@@ -17,7 +17,7 @@
  *    synchronise and are stream-ordered on `stream` (a hipStream_t, NULL = default):
  *    they may be captured into a hipGraph.
  *  - One ag_ctx per process and device; a ctx is not thread-safe.
- *  - Every struct passed by pointer (ag_batch_in, ag_batch_out, ag_lrts_samples,
+ *  - Every struct passed by pointer (ag_batch_in, ag_batch_out, ag_slots_out, ag_lrts_samples,
  *    ag_shading_samples) starts with `struct_size` = sizeof(struct) as the caller compiled
  *    it. A binding written against another layout is refused with AG_ERR_INVALID before
  *    any other field is read (AG_STRUCT_INIT sets it in C).
@@ -136,10 +136,15 @@ typedef struct ag_shape {
   int32_t embedding_size;     /* E: true context dims; D = E + 1 with the intercept      */
   int32_t obs_embedding_size; /* OE: observable dims (src/Auction.py:36)                 */
   int32_t mechanism;          /* ag_mechanism                                            */
-  int32_t num_slots;          /* must be 1 (max_slots is hard-coded, src/main.py:37)     */
+  int32_t num_slots;          /* max_slots of the auction (src/Auction.py:30), 1..AG_MAX_SLOTS;
+                                 src/main.py:37 hard-codes 1. Above 1 the rounds run through
+                                 ag_simulate_slots only                                    */
   int32_t reserved;
   double embedding_var;       /* context ~ N(0, embedding_var) (src/Auction.py:33)       */
 } ag_shape;
+
+/* Most slots an auction may have (ag_shape.num_slots, ag_allocate_slots' max_slots). */
+#define AG_MAX_SLOTS 8
 
 typedef struct ag_ctx ag_ctx;
 
@@ -305,9 +310,73 @@ int ag_allocate(ag_ctx *ctx, const double *bids, int64_t B, int32_t *winner, dou
 
 /* B rounds of Auction.simulate_opportunity (src/Auction.py:28-74) in replay mode.
  * counters_fx: dev int64 [N][AG_NUM_COUNTERS][AG_FX_LIMBS], ACCUMULATED (zero it at the
- * start of an iteration, like Agent.clear_utility); may be NULL. */
+ * start of an iteration, like Agent.clear_utility); may be NULL.
+ * One slot per auction: on a context with num_slots > 1 this, ag_simulate_generated,
+ * ag_lrts_collect and ag_shading_collect return AG_ERR_UNSUPPORTED (use ag_simulate_slots). */
 int ag_simulate(ag_ctx *ctx, int64_t B, const ag_batch_in *in, ag_batch_out *out,
                 int64_t *counters_fx, void *stream);
+
+/* ---- Several slots per auction (src/Auction.py:30, :60-74; src/AuctionAllocation.py:18-35) ----
+ * A round has n = rng.integers(1, max_slots + 1) slots and P participants, ranked by descending
+ * bid, ties to the lower participant slot (a stable descending order: a bid takes a rank only from
+ * bids it strictly exceeds; the reference's np.argsort order among exactly tied bids is not pinned
+ * beyond that). As in the one-slot kernels the bid of participant slot 0 opens the ranking whatever
+ * it is, and a later bid that is NaN or -inf exceeds nothing and is never ranked.
+ *  - rng.binomial(1, CTRs[winners]) draws one click per element of winners, min(n, P) of them;
+ *  - the charge loop's zip stops at the shortest of winners, prices and second prices, so
+ *    F = min(n, P - 1) slots are FILLED (charged); with `sorted` the descending bids, slot k < F has
+ *    FirstPrice price_k = sorted[k], second_k = sorted[k + 1]; SecondPrice price_k = second_k =
+ *    sorted[k + 1]; its click is bernoulli(true CTR of rank k, the k-th consumed double);
+ *  - Agent.set_price reaches every non-winner of every slot, so after the loop EVERY participant's
+ *    logged price is log_price = price_{F-1}, earlier winners included; a winner also logs its own
+ *    slot's second price and click;
+ *  - counters of a record that won rank k < F: GROSS += value * click_k, PAID += price_k, N_WON += 1,
+ *    CTR_BIAS as ag_simulate, OVERBID += log_price - second_k (under BOTH mechanisms: nonzero, even
+ *    negative, under SecondPrice when k < F - 1); of a record that lost: UNDERBID += (log_price -
+ *    bid) * [log_price < true_ctr * value] (log_price 0 when F = 0); the other terms as ag_simulate.
+ * Outputs (dev); any pointer may be NULL. */
+typedef struct ag_slots_out {
+  uint64_t struct_size;  /* sizeof(ag_slots_out)                                            */
+  int32_t *winner;       /* [max_slots][B] participant slot filling slot k; -1 when unfilled  */
+  double *price;         /* [max_slots][B] price_k; NaN when unfilled                        */
+  double *second_price;  /* [max_slots][B] second_k; NaN when unfilled                       */
+  uint8_t *outcome;      /* [max_slots][B] click of slot k; 0 when unfilled                  */
+  double *log_price;     /* [B] price_{F-1}, every participant's logged price; NaN when F = 0 */
+  int32_t *num_filled;   /* [B] F                                                           */
+  int32_t *item;         /* [P][B] as ag_batch_out ...                                      */
+  double *bid;
+  double *est_ctr;
+  double *true_ctr;
+  double *best_ev;
+  double *gamma;
+  double *propensity;
+  int8_t *won_slot;      /* [P][B] the rank the participant won, -1 when it lost (what a record
+                            collector of multi-slot rounds reads, with log_price)            */
+} ag_slots_out;
+
+/* B rounds of Auction.simulate_opportunity with several slots, replay mode. max_slots =
+ * ag_shape.num_slots (1 included: the results are ag_simulate's, with u_slots = u).
+ * num_slots: dev int32 [B], each in 1..max_slots (values outside are clamped into that range);
+ * u_slots: dev [max_slots][B], row k the k-th double rng.binomial consumes -- only the filled
+ * slots' rows, k < F = min(num_slots, P - 1), of an auction are read (the click of an unfilled
+ * slot reaches no log), so an array of min(max_slots, P) rows, as ag_replay_draw_slots fills it,
+ * serves.
+ * in->u is not read and may be NULL. counters_fx as ag_simulate: accumulated, exact, left in normal
+ * form. Any population, any P with E + 1 <= 8; B * max(P, max_slots) < 2^31. Hot call. */
+int ag_simulate_slots(ag_ctx *ctx, int64_t B, const ag_batch_in *in, const int32_t *num_slots,
+                      const double *u_slots, ag_slots_out *out, int64_t *counters_fx, void *stream);
+
+/* Batched AllocationMechanism.allocate(bids, num_slots) (src/AuctionAllocation.py:18-35): bids dev
+ * [P][B], num_slots dev int32 [B] (each in 1..max_slots, clamped; NULL: max_slots for every
+ * auction) -> winner / price / second_price dev [max_slots][B] (any may be NULL): exactly the
+ * arrays the reference returns, padded with -1 (winners) and NaN (prices). With n slots:
+ * winner_k for k < min(n, P); FirstPrice price_k = sorted[k] for k < min(n, P), second_k =
+ * sorted[k + 1] for k < min(n, P - 1); SecondPrice price_k = second_k = sorted[k + 1] for k <
+ * min(n, P - 1). (allocate's own shapes, not the charge loop's F.) Ranking as ag_simulate_slots.
+ * Works on any context (its P and mechanism); max_slots in 1..AG_MAX_SLOTS; P <= 64, otherwise
+ * AG_ERR_UNSUPPORTED. Hot call. */
+int ag_allocate_slots(ag_ctx *ctx, const double *bids, const int32_t *num_slots, int32_t max_slots, int64_t B,
+                      int32_t *winner, double *price, double *second_price, void *stream);
 
 /* Generate mode: B rounds of Auction.simulate_opportunity whose inputs are drawn on the chip
  * inside the simulate kernel, the same bits ag_generate(seed, first_auction, B) -- and, for
@@ -391,6 +460,17 @@ int ag_replay_draw(ag_pcg64_state *rng, int64_t B, int32_t N, int32_t P, int32_t
                    int32_t max_slots, const uint8_t *shading, const double *prev_gamma, const double *gamma_sigma,
                    double *ctx, int32_t *part, double *gamma_raw, double *u);
 
+/* ag_replay_draw for multi-slot rounds: the same draws in the same order, except that the round's
+ * rng.integers(1, max_slots + 1) is kept -- num_slots host int32 [B] -- and rng.binomial(1,
+ * CTRs[winners]) consumes min(num_slots, P) doubles, one per winner in rank order: u_slots host
+ * [min(max_slots, P)][B], row k the k-th consumed double, NaN where nothing is consumed. u (may be
+ * NULL) receives row 0. (ag_replay_draw draws the slots word too but consumes ONE double whatever
+ * it is: right for one slot only.) numpy draws nothing for a winner whose CTR is exactly 0. */
+int ag_replay_draw_slots(ag_pcg64_state *rng, int64_t B, int32_t N, int32_t P, int32_t E, double embedding_var,
+                         int32_t max_slots, const uint8_t *shading, const double *prev_gamma,
+                         const double *gamma_sigma, double *ctx, int32_t *part, double *gamma_raw, double *u,
+                         int32_t *num_slots, double *u_slots);
+
 /* ag_replay_draw_population -- B rounds of a general population's draws, in the reference's
  * order (src/Auction.py:30-42, :65; per participant slot, src/Agent.py:44-53: the LR-TS
  * allocator's Thompson draw torch.normal(0, 1/sqrt(q)) of src/Models.py:31, then the
@@ -428,6 +508,15 @@ int ag_replay_draw_population(ag_pcg64_state *rng, uint8_t *torch_state, int64_t
                               const uint8_t *ts, const float *ts_std, int32_t KDo, const int32_t *ts_kdo,
                               const uint8_t *policy, const uint8_t *search, double *ctx, int32_t *part,
                               double *gamma_raw, double *u, float *ts_noise, float *policy_eps, double *gamma_grid);
+
+/* ag_replay_draw_population for multi-slot rounds: num_slots / u_slots as ag_replay_draw_slots. */
+int ag_replay_draw_population_slots(ag_pcg64_state *rng, uint8_t *torch_state, int64_t torch_state_bytes, int64_t B,
+                                    int32_t N, int32_t P, int32_t E, double embedding_var, int32_t max_slots,
+                                    const uint8_t *shading, const double *prev_gamma, const double *gamma_sigma,
+                                    const uint8_t *ts, const float *ts_std, int32_t KDo, const int32_t *ts_kdo,
+                                    const uint8_t *policy, const uint8_t *search, double *ctx, int32_t *part,
+                                    double *gamma_raw, double *u, float *ts_noise, float *policy_eps,
+                                    double *gamma_grid, int32_t *num_slots, double *u_slots);
 
 /* ---- LR-TS allocator update (Agent.update -> PyTorchLogisticRegressionAllocator.update,
  * src/Agent.py:79-91, src/BidderAllocation.py:29-65) ------------------------------------
