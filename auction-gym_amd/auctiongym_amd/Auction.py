@@ -20,9 +20,13 @@ them is the reference's per-agent loop, src/main.py:127-152).
 
 Several slots (max_slots > 1; src/main.py hard-codes 1, src/Auction.py:30, :60-74 are written for
 more): a round draws its slot count and one click per winner (replay.draw_round_slots) and runs
-through ag_simulate_slots. Populations without learners only -- OracleAllocator + TruthfulBidder
-agents with memory = 0: the record collectors that feed Agent.update do not read multi-slot
-rounds yet.
+through ag_simulate_slots. With learners_on_slots=True learning agents take part: the round's
+draws are draw_round_population's with the slot count kept and one click double per winner
+(replay.draw_round_population_slots), and the records Agent.update trains on are collected per
+launch by ag_lrts_collect_slots / ag_shading_collect_slots (one LR-TS sample per filled slot an LR-TS
+agent won; utilities on the round's logged price); the updates themselves are slot-agnostic.
+Without the flag such an Auction is refused, as it was before those collectors existed; Agent(memory
+> 0) with several slots is refused either way.
 """
 import warnings
 
@@ -32,8 +36,9 @@ import torch
 from . import Agent as _agent_mod
 from . import _lib
 from .engine import TORCH_NORMAL_AVX2, AuctionEngine
-from .replay import (draw_round, draw_round_population, draw_round_slots, draw_rounds_native,
-                     draw_rounds_native_population, draw_rounds_native_slots)
+from .replay import (draw_round, draw_round_population, draw_round_population_slots, draw_round_slots,
+                     draw_rounds_native, draw_rounds_native_population, draw_rounds_native_population_slots,
+                     draw_rounds_native_slots)
 
 C = _agent_mod.C
 
@@ -58,7 +63,8 @@ class Auction:
     FLUSH_ROUNDS_TS = 1 << 16  # Thompson-sampling rounds carry K*(OE+1) floats per slot
 
     def __init__(self, rng, allocation, agents, agent2items, agents2item_values, max_slots,
-                 embedding_size, embedding_var, obs_embedding_size, num_participants_per_round):
+                 embedding_size, embedding_var, obs_embedding_size, num_participants_per_round, *,
+                 learners_on_slots=False):
         self.rng = rng
         self.allocation = allocation
         self.agents = agents
@@ -91,11 +97,19 @@ class Auction:
         bk = np.array([a.bidder.kind for a in agents], np.int32)
         self._shading = bk != _lib.BIDDER_TRUTHFUL
         self._lrts = ak == _lib.ALLOCATOR_LRTS
-        if self._slots and ((ak == _lib.ALLOCATOR_LRTS).any() or (bk != _lib.BIDDER_TRUTHFUL).any()
-                            or any(a.memory != 0 for a in agents)):
+        # learners_on_slots: the default stays the refusal that predates the multi-slot record
+        # collectors -- tests/test_gpu_slots.py::test_auction_refuses_learners_on_several_slots pins
+        # it; flipping the default retires that test
+        if self._slots and not learners_on_slots and (
+                (ak == _lib.ALLOCATOR_LRTS).any() or (bk != _lib.BIDDER_TRUTHFUL).any()
+                or any(a.memory != 0 for a in agents)):
             raise NotImplementedError(
                 f"max_slots = {max_slots} with learning agents or Agent(memory > 0): log-fed updates from "
                 "multi-slot rounds are not built (the LR-TS and shading record collectors read one-slot rounds)")
+        if self._slots and any(a.memory != 0 for a in agents):
+            raise NotImplementedError(
+                f"max_slots = {max_slots} with Agent(memory > 0): the records an agent keeps over clear_logs are "
+                "not rebuilt from multi-slot rounds (no reference capture pins them)")
         self._engine = eng = AuctionEngine(N, num_participants_per_round, K, embedding_size,
                                            obs_embedding_size, allocation.code, embedding_var,
                                            max_slots=int(max_slots))
@@ -186,11 +200,20 @@ class Auction:
     # ------------------------------------------------------------------ rounds
     def _draw_round(self):
         N, P = len(self.agents), self.num_participants_per_round
-        if self._slots:  # (no learners: nothing else draws)
-            self._pending.append(draw_round_slots(self.rng, N, P, self.embedding_size, self.embedding_var,
-                                                  self.max_slots))
+        plain = not (self._shading.any() or (self._lrts.any() and self._ts))  # nothing else draws
+        if self._slots:  # rows (ctx, part, u_slots, gamma_raw, ts_noise, policy_eps, gamma_grid, n)
+            if plain:
+                ctx, part, n, us = draw_round_slots(self.rng, N, P, self.embedding_size, self.embedding_var,
+                                                    self.max_slots)
+                self._pending.append((ctx, part, us, None, None, None, None, n))
+                return
+            shading, models, policy, search = self._population_draws()
+            ctx, part, g, us, noise, eps, grid, n = draw_round_population_slots(
+                self.rng, N, P, self.embedding_size, self.embedding_var, shading, models, self.max_slots,
+                policy, search, kdo_max=self._engine.K * (self.obs_embedding_size + 1))
+            self._pending.append((ctx, part, us, g, noise, eps, grid, n))
             return
-        if not (self._shading.any() or (self._lrts.any() and self._ts)):
+        if plain:
             ctx, part, u = draw_round(self.rng, N, P, self.embedding_size, self.embedding_var,
                                       self.max_slots)
             self._pending.append((ctx, part, u, None, None, None, None))
@@ -265,15 +288,6 @@ class Auction:
             return
         self._flush()
         N, P = len(self.agents), self.num_participants_per_round
-        if self._slots:
-            d = self._engine.device
-            for lo in range(0, B, self.NATIVE_ROUNDS):
-                n = min(self.NATIVE_ROUNDS, B - lo)
-                ctx, part, _, ns, us = draw_rounds_native_slots(self.rng, n, N, P, self.embedding_size,
-                                                                self.embedding_var, self.max_slots)
-                self._run_slots({"ctx": torch.from_numpy(ctx).to(d), "part": torch.from_numpy(part).to(d)},
-                                torch.from_numpy(ns).to(d), torch.from_numpy(us).to(d))
-            return
         shading, models, policy, search = self._population_draws()
         torch_or_grid = (any(m is not None for m in models) or (policy is not None and any(policy))
                          or (search is not None and any(search)))
@@ -284,17 +298,27 @@ class Auction:
         d = self._engine.device
         for lo in range(0, B, step):
             n = min(step, B - lo)
+            ns = us = None
             if torch_or_grid:
-                ctx, part, g, u, noise, eps, grid = draw_rounds_native_population(
-                    self.rng, n, N, P, self.embedding_size, self.embedding_var,
-                    shading if self._shading.any() else None, models, self.max_slots, policy, search,
-                    kdo_max=self._engine.K * (self.obs_embedding_size + 1))
+                draw = draw_rounds_native_population_slots if self._slots else draw_rounds_native_population
+                drawn = draw(self.rng, n, N, P, self.embedding_size, self.embedding_var,
+                             shading if self._shading.any() else None, models, self.max_slots, policy, search,
+                             kdo_max=self._engine.K * (self.obs_embedding_size + 1))
+                ctx, part, g, u, noise, eps, grid = drawn[:7]
+                if self._slots:
+                    ns, us = drawn[7:]
+            elif self._slots:
+                ctx, part, g, ns, us = draw_rounds_native_slots(self.rng, n, N, P, self.embedding_size,
+                                                                self.embedding_var, self.max_slots,
+                                                                shading if self._shading.any() else None)
+                u = noise = eps = grid = None
             else:
                 ctx, part, u, g = draw_rounds_native(self.rng, n, N, P, self.embedding_size, self.embedding_var,
                                                      self.max_slots, shading if self._shading.any() else None)
                 noise = eps = grid = None
-            inp = {"ctx": torch.from_numpy(ctx).to(d), "part": torch.from_numpy(part).to(d),
-                   "u": torch.from_numpy(u).to(d)}
+            inp = {"ctx": torch.from_numpy(ctx).to(d), "part": torch.from_numpy(part).to(d)}
+            if not self._slots:
+                inp["u"] = torch.from_numpy(u).to(d)
             if self._shading.any():
                 inp["gamma_raw"] = torch.from_numpy(g).to(d)
             if self._learning.any():
@@ -304,7 +328,10 @@ class Auction:
                     inp["gamma_grid"] = torch.from_numpy(grid).to(d)
             if self._lrts.any() and self._ts:
                 inp["ts_noise"] = torch.from_numpy(noise).to(d)
-            self._run(inp)
+            if self._slots:
+                self._run_slots(inp, torch.from_numpy(ns).to(d), torch.from_numpy(us).to(d))
+            else:
+                self._run(inp)
 
     def simulate_synthetic(self, B, seed, first_auction=0):
         """B rounds with on-device Philox inputs (throughput mode; parity via the oracle)."""
@@ -336,19 +363,13 @@ class Auction:
         d, P = self._engine.device, self.num_participants_per_round
         rows, self._pending = self._pending, []
         B = len(rows)
-        if self._slots:
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d)  # noqa: E731
-            self._run_slots({"ctx": up(np.stack([r[0] for r in rows], axis=1)),
-                             "part": up(np.stack([r[1] for r in rows], axis=1).astype(np.int32))},
-                            up(np.array([r[2] for r in rows], np.int32)), up(np.stack([r[3] for r in rows], axis=1)))
-            return
         ctx = np.empty((self.embedding_size, B))
         part = np.empty((P, B), np.int32)
-        u = np.empty(B)
-        for r, (c, p, uu, _, _, _, _) in enumerate(rows):
-            ctx[:, r], part[:, r], u[r] = c, p, uu
-        inp = {"ctx": torch.from_numpy(ctx).to(d), "part": torch.from_numpy(part).to(d),
-               "u": torch.from_numpy(u).to(d)}
+        for r, row in enumerate(rows):
+            ctx[:, r], part[:, r] = row[0], row[1]
+        inp = {"ctx": torch.from_numpy(ctx).to(d), "part": torch.from_numpy(part).to(d)}
+        if not self._slots:
+            inp["u"] = torch.from_numpy(np.array([row[2] for row in rows], np.float64)).to(d)
         if self._shading.any():
             g = np.stack([row[3] for row in rows], axis=1)
             inp["gamma_raw"] = torch.from_numpy(np.ascontiguousarray(g)).to(d)
@@ -371,6 +392,11 @@ class Auction:
                 if row[4] is not None:
                     z[r] = row[4]
             inp["ts_noise"] = torch.from_numpy(AuctionEngine.tile_ts_noise(z)).to(d)
+        if self._slots:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d)  # noqa: E731
+            self._run_slots(inp, up(np.array([row[7] for row in rows], np.int32)),
+                            up(np.stack([row[2] for row in rows], axis=1)))
+            return
         self._run(inp)
 
     def _run(self, inp):
@@ -408,10 +434,15 @@ class Auction:
             hi = min(B, lo + max_b)
             if hi - lo == B:
                 eng.simulate_slots(inp, num_slots, u_slots, out, cnt)
+                if self._learner.any():
+                    self._collect(inp, out, B, self._logged_rounds, slots=True)
                 continue
+            sl_in = {k: (v[..., lo:hi].contiguous() if k != "ts_noise"
+                         else v[:, lo // 64:(hi + 63) // 64].contiguous()) for k, v in inp.items()}
             sl_out = {k: torch.empty(v[..., lo:hi].shape, dtype=v.dtype, device=v.device) for k, v in out.items()}
-            eng.simulate_slots({k: v[..., lo:hi].contiguous() for k, v in inp.items()},
-                               num_slots[lo:hi].contiguous(), u_slots[:, lo:hi].contiguous(), sl_out, cnt)
+            eng.simulate_slots(sl_in, num_slots[lo:hi].contiguous(), u_slots[:, lo:hi].contiguous(), sl_out, cnt)
+            if self._learner.any():
+                self._collect(sl_in, sl_out, hi - lo, self._logged_rounds + lo, slots=True)
             for k, v in out.items():
                 v[..., lo:hi].copy_(sl_out[k])
         self._account(cnt, inp, out, B)
@@ -459,18 +490,27 @@ class Auction:
         self._stores[name] = st
         return st
 
-    def _collect(self, inp, out, B, first_auction):
+    def _collect(self, inp, out, B, first_auction, slots=False):
+        """The learners' records of a launch into the device stores; slots: `out` is ag_slots_out's
+        (an auction then holds up to min(max_slots, P - 1) won LR-TS samples, not one)."""
         eng = self._engine
+        P = self.num_participants_per_round
         if self._lrts.any():
-            need = self._bounds["lrts"] + B
+            need = self._bounds["lrts"] + (B * min(int(self.max_slots), max(P - 1, 0)) if slots else B)
             st = self._grow("lrts", need, eng.new_lrts_samples)
-            eng.lrts_collect(inp, out, st)
+            if slots:
+                eng.lrts_collect_slots(inp, out, st)
+            else:
+                eng.lrts_collect(inp, out, st)
             self._bounds["lrts"] = need
         if self._shading_rec.any():
-            need = self._bounds["shading"] + B * self.num_participants_per_round
+            need = self._bounds["shading"] + B * P
             learning = bool(self._learning.any())
             st = self._grow("shading", need, lambda cap: eng.new_shading_samples(cap, learning=learning))
-            eng.shading_collect(inp, out, st, first_auction=first_auction)
+            if slots:
+                eng.shading_collect_slots(inp, out, st, first_auction=first_auction)
+            else:
+                eng.shading_collect(inp, out, st, first_auction=first_auction)
             self._bounds["shading"] = need
 
     def _update_agent(self, index, iteration):

@@ -45,6 +45,19 @@ def _batch_out(outputs):
     return AgBatchOut(*[_ptr(outputs.get(f)).value for f in _OUT_FIELDS])
 
 
+def _slots_out(outputs):
+    return AgSlotsOut(*[_ptr(outputs.get(f)).value for f in _SLOT_FIELDS])
+
+
+def _slots_batch(inputs, outputs):
+    """B of a multi-slot batch: the last dimension of whichever array is there (a missing required
+    one is the library's error to report)."""
+    for t in [inputs.get("part"), inputs.get("ctx")] + [outputs.get(f) for f in _SLOT_FIELDS]:
+        if t is not None:
+            return t.shape[-1]
+    return 0
+
+
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
@@ -370,9 +383,31 @@ class AuctionEngine:
                 or u_slots.shape[1] != B or u_slots.shape[0] < min(self.max_slots, self.P)):
             raise ValueError("num_slots must be int32 [B], u_slots float64 [min(max_slots, P)][B]")
         bi = _batch_in(inputs)
-        so = AgSlotsOut(*[_ptr(outputs.get(f)).value for f in _SLOT_FIELDS])
+        so = _slots_out(outputs)
         self._check(self.L.ag_simulate_slots(self._h, B, ctypes.byref(bi), _ptr(num_slots), _ptr(u_slots),
                                              ctypes.byref(so), _ptr(counters), _stream()), "ag_simulate_slots")
+
+    def lrts_collect_slots(self, inputs, slot_outputs, store):
+        """Append the won LR-TS samples of a batch of multi-slot rounds (ag_lrts_collect_slots):
+        one per filled slot whose winner is an LR-TS allocator, so up to
+        B * min(max_slots, max(P - 1, 0)) records. inputs / slot_outputs as simulate_slots."""
+        B = _slots_batch(inputs, slot_outputs)
+        bi = _batch_in(inputs)
+        so = _slots_out(slot_outputs)
+        st = self._samples(store)
+        self._check(self.L.ag_lrts_collect_slots(self._h, B, ctypes.byref(bi), ctypes.byref(so), ctypes.byref(st),
+                                                 _stream()), "ag_lrts_collect_slots")
+
+    def shading_collect_slots(self, inputs, slot_outputs, store, first_auction=0):
+        """Append the non-truthful bidders' records of a batch of multi-slot rounds, auctions
+        [first_auction, first_auction + B) (ag_shading_collect_slots): up to B * P records."""
+        B = _slots_batch(inputs, slot_outputs)
+        bi = _batch_in(inputs)
+        so = _slots_out(slot_outputs)
+        st = self._shading(store)
+        self._check(self.L.ag_shading_collect_slots(self._h, int(first_auction), B, ctypes.byref(bi),
+                                                    ctypes.byref(so), ctypes.byref(st), _stream()),
+                    "ag_shading_collect_slots")
 
     def allocate_slots(self, bids, num_slots=None, max_slots=None):
         """Batched allocate(bids, num_slots) (ag_allocate_slots): bids float64 [P][B], num_slots

@@ -93,12 +93,12 @@ def instantiate_agents(rng, agent_configs, agents2item_values, agents2items):
 
 
 def instantiate_auction(rng, config, agents2items, agents2item_values, agents, max_slots,
-                        embedding_size, embedding_var, obs_embedding_size):
-    """src/main.py:98-109."""
+                        embedding_size, embedding_var, obs_embedding_size, learners_on_slots=False):
+    """src/main.py:98-109. learners_on_slots: accept learning agents with max_slots > 1 (Auction)."""
     allocation = make_plugin(config["allocation"], rng, {}, pass_rng=False)
     auction = Auction(rng, allocation, agents, agents2items, agents2item_values, max_slots,
                       embedding_size, embedding_var, obs_embedding_size,
-                      config["num_participants_per_round"])
+                      config["num_participants_per_round"], learners_on_slots=learners_on_slots)
     return auction, config["num_iter"], config["rounds_per_iter"], config["output_dir"]
 
 

@@ -312,7 +312,8 @@ int ag_allocate(ag_ctx *ctx, const double *bids, int64_t B, int32_t *winner, dou
  * counters_fx: dev int64 [N][AG_NUM_COUNTERS][AG_FX_LIMBS], ACCUMULATED (zero it at the
  * start of an iteration, like Agent.clear_utility); may be NULL.
  * One slot per auction: on a context with num_slots > 1 this, ag_simulate_generated,
- * ag_lrts_collect and ag_shading_collect return AG_ERR_UNSUPPORTED (use ag_simulate_slots). */
+ * ag_lrts_collect and ag_shading_collect return AG_ERR_UNSUPPORTED (use ag_simulate_slots,
+ * ag_lrts_collect_slots and ag_shading_collect_slots). */
 int ag_simulate(ag_ctx *ctx, int64_t B, const ag_batch_in *in, ag_batch_out *out,
                 int64_t *counters_fx, void *stream);
 
@@ -365,6 +366,36 @@ typedef struct ag_slots_out {
  * form. Any population, any P with E + 1 <= 8; B * max(P, max_slots) < 2^31. Hot call. */
 int ag_simulate_slots(ag_ctx *ctx, int64_t B, const ag_batch_in *in, const int32_t *num_slots,
                       const double *u_slots, ag_slots_out *out, int64_t *counters_fx, void *stream);
+
+/* The record collectors of multi-slot rounds: what Agent.update reads from the logs of B rounds of
+ * ag_simulate_slots (src/Auction.py:68-74, src/Agent.py:70-94), appended to the stores of
+ * ag_lrts_samples / ag_shading_samples (declared below with the one-slot collectors and the
+ * updates; everything downstream of a store is slot-agnostic). `in` / `out` are the arrays
+ * ag_simulate_slots read and wrote. They work on any context, num_slots = 1 included (there the
+ * records are ag_lrts_collect's / ag_shading_collect's on ag_simulate's outputs, as multisets).
+ * Hot calls: stream-ordered, no synchronisation. Records are unordered; records beyond `capacity`
+ * are dropped while *count still advances (the updates report the overflow).
+ *
+ * ag_lrts_collect_slots: one record per FILLED slot k < F = num_filled whose winner is an LR-TS
+ * allocator (Agent.update's won_mask): key = agent << 16 | item << 1 | outcome[k], x = the
+ * float32 observed context, 1.0. The rank-F participant (a click draw, no charge) is no record;
+ * P = 1 collects nothing. At most B * min(max_slots, max(P - 1, 0)) records per call. Needs
+ * in.ctx, in.part, out.winner, out.outcome, out.num_filled, out.item (AG_ERR_INVALID otherwise).
+ *
+ * ag_shading_collect_slots: one record per participation of a non-truthful bidder, of auctions
+ * [first_auction, first_auction + B): won = (won_slot = k >= 0); utility = value * outcome[k] -
+ * log_price if won, else 0 -- the round's LOGGED price, not the winner's own price_k
+ * (src/Bidder.py:62-63 read the log set_price wrote last); order = (first_auction + i) * P + s;
+ * gamma, ctr, value, propensity as ag_shading_collect. F = 0 (P = 1): won = 0, utility = 0 (the
+ * NaN log_price is not stored). Exactly the non-truthful participations, at most B * P records
+ * per call. Needs in.part, out.won_slot, out.log_price, out.outcome, out.item, out.gamma, and
+ * out.est_ctr / out.propensity when the store has ctr / propensity (AG_ERR_INVALID otherwise). */
+struct ag_lrts_samples;
+struct ag_shading_samples;
+int ag_lrts_collect_slots(ag_ctx *ctx, int64_t B, const ag_batch_in *in, const ag_slots_out *out,
+                          const struct ag_lrts_samples *samples, void *stream);
+int ag_shading_collect_slots(ag_ctx *ctx, int64_t first_auction, int64_t B, const ag_batch_in *in,
+                             const ag_slots_out *out, const struct ag_shading_samples *samples, void *stream);
 
 /* Batched AllocationMechanism.allocate(bids, num_slots) (src/AuctionAllocation.py:18-35): bids dev
  * [P][B], num_slots dev int32 [B] (each in 1..max_slots, clamped; NULL: max_slots for every
