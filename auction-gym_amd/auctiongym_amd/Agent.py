@@ -233,52 +233,41 @@ class Agent:
 def _records(part, out, ctx, agent, first_round, values, obs=None):
     """Build ImpressionOpportunity rows of `agent` from host copies of one batch. ctx [E][B]:
     the record's context is the true context + intercept, or (obs = OE) its first OE entries
-    + intercept (src/Auction.py:33-36)."""
+    + intercept (src/Auction.py:33-36).
+
+    `out` in either layout. ag_batch_out's (one slot): the winner, its click and second price per
+    round; nobody wins and nothing is charged at P == 1. ag_slots_out's ("won_slot" in out;
+    src/Auction.py:68-74): set_price reaches every non-winner of every filled slot, so every
+    participant's logged price is the last filled slot's (log_price; 0.0 when no slot was filled);
+    a winner logs its own slot's second price and click."""
     recs = []
     P, B = part.shape
     if "won_slot" in out:
-        return _records_slots(part, out, ctx, agent, values, obs)
-    for r in range(B):
-        for s in range(P):
-            if part[s, r] != agent:
-                continue
-            charged = P >= 2
-            won = charged and out["winner"][r] == s
-            it = int(out["item"][s, r])
-            c = ctx[:, r] if obs is None else ctx[:obs, r]
-            recs.append(ImpressionOpportunity(
-                context=np.concatenate((c, [1.0])), item=it, value=float(values[agent][it]),
-                bid=float(out["bid"][s, r]),
-                best_expected_value=float(out["best_ev"][s, r]),
-                true_CTR=float(out["true_ctr"][s, r]), estimated_CTR=float(out["est_ctr"][s, r]),
-                price=float(out["price"][r]) if charged else 0.0,
-                second_price=float(out["second_price"][r]) if won else 0.0,
-                outcome=bool(out["outcome"][r]) if won else False, won=bool(won)))
-    return recs
-
-
-def _records_slots(part, out, ctx, agent, values, obs=None):
-    """_records for multi-slot rounds (ag_slots_out; src/Auction.py:68-74): set_price reaches
-    every non-winner of every filled slot, so every participant's logged price is the last filled
-    slot's (log_price; 0.0 when no slot was filled); a winner logs its own slot's second price
-    and click."""
-    recs = []
-    P, B = part.shape
-    for r in range(B):
-        for s in range(P):
-            if part[s, r] != agent:
-                continue
+        def won_at(s, r):  # -> won, the index of the winner's second_price / outcome
             k = int(out["won_slot"][s, r])
-            won = k >= 0
+            return k >= 0, (k, r)
+
+        def logged_price(r):
+            return float(out["log_price"][r]) if out["num_filled"][r] > 0 else 0.0
+    else:
+        def won_at(s, r):
+            return bool(P >= 2 and out["winner"][r] == s), r
+
+        def logged_price(r):
+            return float(out["price"][r]) if P >= 2 else 0.0
+    for r in range(B):
+        for s in range(P):
+            if part[s, r] != agent:
+                continue
+            won, w = won_at(s, r)
             it = int(out["item"][s, r])
             c = ctx[:, r] if obs is None else ctx[:obs, r]
             recs.append(ImpressionOpportunity(
                 context=np.concatenate((c, [1.0])), item=it, value=float(values[agent][it]),
                 bid=float(out["bid"][s, r]), best_expected_value=float(out["best_ev"][s, r]),
                 true_CTR=float(out["true_ctr"][s, r]), estimated_CTR=float(out["est_ctr"][s, r]),
-                price=float(out["log_price"][r]) if out["num_filled"][r] > 0 else 0.0,
-                second_price=float(out["second_price"][k, r]) if won else 0.0,
-                outcome=bool(out["outcome"][k, r]) if won else False, won=won))
+                price=logged_price(r), second_price=float(out["second_price"][w]) if won else 0.0,
+                outcome=bool(out["outcome"][w]) if won else False, won=won))
     return recs
 
 

@@ -29,6 +29,7 @@ Without the flag such an Auction is refused, as it was before those collectors e
 > 0) with several slots is refused either way.
 """
 import warnings
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -36,11 +37,24 @@ import torch
 from . import Agent as _agent_mod
 from . import _lib
 from .engine import TORCH_NORMAL_AVX2, AuctionEngine
-from .replay import (draw_round, draw_round_population, draw_round_population_slots, draw_round_slots,
-                     draw_rounds_native, draw_rounds_native_population, draw_rounds_native_population_slots,
+from .replay import (draw_round_population_slots, draw_round_slots, draw_rounds_native_population_slots,
                      draw_rounds_native_slots)
 
 C = _agent_mod.C
+
+
+class Draws(NamedTuple):
+    """The random inputs of one pending round, or of a batch of B rounds as host SoA arrays (the
+    batch's shapes in brackets). A one-slot round has num_slots = 1 and a length-1 u_slots: at
+    max_slots = 1 the *_slots draws are the one-slot draws (tests/test_host_slots.py)."""
+    ctx: np.ndarray        # [E] ([E][B])
+    part: np.ndarray       # [P] ([P][B])
+    num_slots: object      # the round's slot count ([B] int32)
+    u_slots: np.ndarray    # [min(max_slots, P)] click doubles, NaN where none is consumed ([..][B])
+    gamma_raw: object      # [P] ([P][B]), or None without shading bidders
+    ts_noise: object       # [P][K*Do] (the kernel's tiles [P][ceil(B/64)][K*Do][64]), or None
+    policy_eps: object     # [P] ([P][B]) float32, or None
+    gamma_grid: object     # [P][128] ([P][128][B]), or None
 
 
 def warn_unpinned_catalogue(K, D, stacklevel=2):
@@ -200,29 +214,16 @@ class Auction:
     # ------------------------------------------------------------------ rounds
     def _draw_round(self):
         N, P = len(self.agents), self.num_participants_per_round
-        plain = not (self._shading.any() or (self._lrts.any() and self._ts))  # nothing else draws
-        if self._slots:  # rows (ctx, part, u_slots, gamma_raw, ts_noise, policy_eps, gamma_grid, n)
-            if plain:
-                ctx, part, n, us = draw_round_slots(self.rng, N, P, self.embedding_size, self.embedding_var,
-                                                    self.max_slots)
-                self._pending.append((ctx, part, us, None, None, None, None, n))
-                return
-            shading, models, policy, search = self._population_draws()
-            ctx, part, g, us, noise, eps, grid, n = draw_round_population_slots(
-                self.rng, N, P, self.embedding_size, self.embedding_var, shading, models, self.max_slots,
-                policy, search, kdo_max=self._engine.K * (self.obs_embedding_size + 1))
-            self._pending.append((ctx, part, us, g, noise, eps, grid, n))
-            return
-        if plain:
-            ctx, part, u = draw_round(self.rng, N, P, self.embedding_size, self.embedding_var,
-                                      self.max_slots)
-            self._pending.append((ctx, part, u, None, None, None, None))
+        if not (self._shading.any() or (self._lrts.any() and self._ts)):  # nothing else draws
+            ctx, part, n, us = draw_round_slots(self.rng, N, P, self.embedding_size, self.embedding_var,
+                                                self.max_slots)
+            self._pending.append(Draws(ctx, part, n, us, None, None, None, None))
             return
         shading, models, policy, search = self._population_draws()
-        ctx, part, g, u, noise, eps, grid = draw_round_population(
+        ctx, part, g, us, noise, eps, grid, n = draw_round_population_slots(
             self.rng, N, P, self.embedding_size, self.embedding_var, shading, models, self.max_slots,
             policy, search, kdo_max=self._engine.K * (self.obs_embedding_size + 1))
-        self._pending.append((ctx, part, u, g, noise, eps, grid))
+        self._pending.append(Draws(ctx, part, n, us, g, noise, eps, grid))
 
     def _flush_limit(self):
         return self.FLUSH_ROUNDS_TS if (self._lrts.any() and self._ts) else self.FLUSH_ROUNDS
@@ -274,8 +275,8 @@ class Auction:
 
     def simulate_batch(self, B):
         """B rounds with the reference's draws, run as one batch. With numpy's PCG64 generator
-        every draw is made in C for the whole batch (replay.draw_rounds_native /
-        draw_rounds_native_population: the same numbers and the same numpy and torch generator
+        every draw is made in C for the whole batch (replay.draw_rounds_native_slots /
+        draw_rounds_native_population_slots: the same numbers and the same numpy and torch generator
         states afterwards as the per-round loop); otherwise the per-round Python loop."""
         B = int(B)
         self._settle_lrts()
@@ -295,43 +296,18 @@ class Auction:
         # transforms (plus the tiled noise): bounded per chunk, whatever P
         step = (max(1 << 12, (self.NATIVE_ROUNDS_TS * 2) // P) if (self._lrts.any() and self._ts)
                 else self.NATIVE_ROUNDS)
-        d = self._engine.device
+        sh = shading if self._shading.any() else None
         for lo in range(0, B, step):
             n = min(step, B - lo)
-            ns = us = None
             if torch_or_grid:
-                draw = draw_rounds_native_population_slots if self._slots else draw_rounds_native_population
-                drawn = draw(self.rng, n, N, P, self.embedding_size, self.embedding_var,
-                             shading if self._shading.any() else None, models, self.max_slots, policy, search,
-                             kdo_max=self._engine.K * (self.obs_embedding_size + 1))
-                ctx, part, g, u, noise, eps, grid = drawn[:7]
-                if self._slots:
-                    ns, us = drawn[7:]
-            elif self._slots:
+                ctx, part, g, _, noise, eps, grid, ns, us = draw_rounds_native_population_slots(
+                    self.rng, n, N, P, self.embedding_size, self.embedding_var, sh, models, self.max_slots, policy,
+                    search, kdo_max=self._engine.K * (self.obs_embedding_size + 1))
+            else:
                 ctx, part, g, ns, us = draw_rounds_native_slots(self.rng, n, N, P, self.embedding_size,
-                                                                self.embedding_var, self.max_slots,
-                                                                shading if self._shading.any() else None)
-                u = noise = eps = grid = None
-            else:
-                ctx, part, u, g = draw_rounds_native(self.rng, n, N, P, self.embedding_size, self.embedding_var,
-                                                     self.max_slots, shading if self._shading.any() else None)
+                                                                self.embedding_var, self.max_slots, sh)
                 noise = eps = grid = None
-            inp = {"ctx": torch.from_numpy(ctx).to(d), "part": torch.from_numpy(part).to(d)}
-            if not self._slots:
-                inp["u"] = torch.from_numpy(u).to(d)
-            if self._shading.any():
-                inp["gamma_raw"] = torch.from_numpy(g).to(d)
-            if self._learning.any():
-                inp["policy_eps"] = (torch.from_numpy(eps).to(d) if eps is not None else
-                                     torch.zeros((P, n), dtype=torch.float32, device=d))
-                if grid is not None:
-                    inp["gamma_grid"] = torch.from_numpy(grid).to(d)
-            if self._lrts.any() and self._ts:
-                inp["ts_noise"] = torch.from_numpy(noise).to(d)
-            if self._slots:
-                self._run_slots(inp, torch.from_numpy(ns).to(d), torch.from_numpy(us).to(d))
-            else:
-                self._run(inp)
+            self._run(self._device_inputs(Draws(ctx, part, ns, us, g, noise, eps, grid)))
 
     def simulate_synthetic(self, B, seed, first_auction=0):
         """B rounds with on-device Philox inputs (throughput mode; parity via the oracle)."""
@@ -360,91 +336,82 @@ class Auction:
     def _flush(self):
         if not self._pending:
             return
-        d, P = self._engine.device, self.num_participants_per_round
+        P = self.num_participants_per_round
         rows, self._pending = self._pending, []
         B = len(rows)
-        ctx = np.empty((self.embedding_size, B))
-        part = np.empty((P, B), np.int32)
-        for r, row in enumerate(rows):
-            ctx[:, r], part[:, r] = row[0], row[1]
-        inp = {"ctx": torch.from_numpy(ctx).to(d), "part": torch.from_numpy(part).to(d)}
-        if not self._slots:
-            inp["u"] = torch.from_numpy(np.array([row[2] for row in rows], np.float64)).to(d)
-        if self._shading.any():
-            g = np.stack([row[3] for row in rows], axis=1)
-            inp["gamma_raw"] = torch.from_numpy(np.ascontiguousarray(g)).to(d)
-        if self._learning.any():
-            e = np.zeros((P, B), np.float32)
+
+        def every(field, dtype):
+            """A field every round has, as [..][B]."""
+            return np.ascontiguousarray(np.stack([getattr(row, field) for row in rows], axis=-1), dtype=dtype)
+
+        def some(field, shape, dtype, dense=False):
+            """A field some rounds draw, as [..][B]: zeros where a round drew none; None where none
+            did, unless dense."""
+            if not dense and all(getattr(row, field) is None for row in rows):
+                return None
+            a = np.zeros(shape + (B,), dtype)
             for r, row in enumerate(rows):
-                if row[5] is not None:
-                    e[:, r] = row[5]
-            inp["policy_eps"] = torch.from_numpy(e).to(d)
-            if any(row[6] is not None for row in rows):
-                gg = np.zeros((P, 128, B))
-                for r, row in enumerate(rows):
-                    if row[6] is not None:
-                        gg[:, :, r] = row[6]
-                inp["gamma_grid"] = torch.from_numpy(gg).to(d)
+                if getattr(row, field) is not None:
+                    a[..., r] = getattr(row, field)
+            return a
+
+        noise = None
         if self._lrts.any() and self._ts:
-            KDo = self._engine.K * (self.obs_embedding_size + 1)
-            z = np.zeros((B, P, KDo), np.float32)
-            for r, row in enumerate(rows):
-                if row[4] is not None:
-                    z[r] = row[4]
-            inp["ts_noise"] = torch.from_numpy(AuctionEngine.tile_ts_noise(z)).to(d)
+            z = some("ts_noise", (P, self._engine.K * (self.obs_embedding_size + 1)), np.float32, dense=True)
+            noise = AuctionEngine.tile_ts_noise(np.ascontiguousarray(np.moveaxis(z, -1, 0)))
+        self._run(self._device_inputs(Draws(
+            every("ctx", np.float64), every("part", np.int32), every("num_slots", np.int32),
+            every("u_slots", np.float64), every("gamma_raw", np.float64) if self._shading.any() else None, noise,
+            some("policy_eps", (P,), np.float32), some("gamma_grid", (P, 128), np.float64))))
+
+    def _device_inputs(self, draws):
+        """A drawn batch (Draws of host SoA arrays) as what _run takes: the engine's device inputs,
+        with num_slots [B] and u_slots [min(max_slots, P)][B] beside them. The one place where
+        one-slot rounds differ: their click double is the engine's inp["u"], u_slots' only row."""
+        d = self._engine.device
+        up = lambda a: torch.from_numpy(a).to(d)  # noqa: E731
+        inp = {"ctx": up(draws.ctx), "part": up(draws.part)}
+        if self._shading.any():
+            inp["gamma_raw"] = up(draws.gamma_raw)
+        if self._learning.any():
+            inp["policy_eps"] = (up(draws.policy_eps) if draws.policy_eps is not None else
+                                 torch.zeros(draws.part.shape, dtype=torch.float32, device=d))
+            if draws.gamma_grid is not None:
+                inp["gamma_grid"] = up(draws.gamma_grid)
+        if self._lrts.any() and self._ts:
+            inp["ts_noise"] = up(draws.ts_noise)
         if self._slots:
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d)  # noqa: E731
-            self._run_slots(inp, up(np.array([row[7] for row in rows], np.int32)),
-                            up(np.stack([row[2] for row in rows], axis=1)))
-            return
-        self._run(inp)
+            inp["num_slots"], inp["u_slots"] = up(draws.num_slots), up(draws.u_slots)
+        else:
+            inp["u"] = up(draws.u_slots[0])
+        return inp
 
     def _run(self, inp):
+        """A batch of rounds: inp ctx [E][B], part [P][B], ...; one slot (ag_simulate) with u [B],
+        several (ag_simulate_slots) with num_slots [B] and u_slots [min(max_slots, P)][B]."""
         eng = self._engine
-        B = inp["u"].shape[0]
-        out = eng.alloc_outputs(B)
+        B = inp["part"].shape[1]
+        out = eng.alloc_slot_outputs(B) if self._slots else eng.alloc_outputs(B)
         cnt = eng.new_counters()
         max_b = 2048 * 8192
         for lo in range(0, B, max_b):
             hi = min(B, lo + max_b)
-            if hi - lo == B:
+            if hi - lo == B:  # the whole batch in one launch: no slice copies
                 sl_in, sl_out = inp, out
             else:  # kernels need contiguous SoA slices
                 sl_in = {k: (v[..., lo:hi].contiguous() if k != "ts_noise"
                              else v[:, lo // 64:(hi + 63) // 64].contiguous()) for k, v in inp.items()}
                 sl_out = {k: torch.empty(v[..., lo:hi].shape, dtype=v.dtype, device=v.device)
                           for k, v in out.items()}
-            eng.simulate(sl_in, sl_out, cnt)
+            if self._slots:
+                eng.simulate_slots(sl_in, sl_in["num_slots"], sl_in["u_slots"], sl_out, cnt)
+            else:
+                eng.simulate(sl_in, sl_out, cnt)
             if self._learner.any():
                 self._collect(sl_in, sl_out, hi - lo, self._logged_rounds + lo)
             if sl_out is not out:
                 for k, v in out.items():
                     v[..., lo:hi].copy_(sl_out[k])
-        self._account(cnt, inp, out, B)
-
-    def _run_slots(self, inp, num_slots, u_slots):
-        """A batch of multi-slot rounds (ag_simulate_slots): inp ctx [E][B], part [P][B]; num_slots
-        [B]; u_slots [min(max_slots, P)][B]."""
-        eng = self._engine
-        B = num_slots.shape[0]
-        out = eng.alloc_slot_outputs(B)
-        cnt = eng.new_counters()
-        max_b = 2048 * 8192
-        for lo in range(0, B, max_b):
-            hi = min(B, lo + max_b)
-            if hi - lo == B:
-                eng.simulate_slots(inp, num_slots, u_slots, out, cnt)
-                if self._learner.any():
-                    self._collect(inp, out, B, self._logged_rounds, slots=True)
-                continue
-            sl_in = {k: (v[..., lo:hi].contiguous() if k != "ts_noise"
-                         else v[:, lo // 64:(hi + 63) // 64].contiguous()) for k, v in inp.items()}
-            sl_out = {k: torch.empty(v[..., lo:hi].shape, dtype=v.dtype, device=v.device) for k, v in out.items()}
-            eng.simulate_slots(sl_in, num_slots[lo:hi].contiguous(), u_slots[:, lo:hi].contiguous(), sl_out, cnt)
-            if self._learner.any():
-                self._collect(sl_in, sl_out, hi - lo, self._logged_rounds + lo, slots=True)
-            for k, v in out.items():
-                v[..., lo:hi].copy_(sl_out[k])
         self._account(cnt, inp, out, B)
 
     def _account(self, cnt, inp, out, B):
@@ -490,27 +457,23 @@ class Auction:
         self._stores[name] = st
         return st
 
-    def _collect(self, inp, out, B, first_auction, slots=False):
-        """The learners' records of a launch into the device stores; slots: `out` is ag_slots_out's
-        (an auction then holds up to min(max_slots, P - 1) won LR-TS samples, not one)."""
+    def _collect(self, inp, out, B, first_auction):
+        """The learners' records of a launch into the device stores. On several slots `out` is
+        ag_slots_out's, and an auction holds up to min(max_slots, P - 1) won LR-TS samples, not one."""
         eng = self._engine
         P = self.num_participants_per_round
+        lrts_collect, shading_collect = ((eng.lrts_collect_slots, eng.shading_collect_slots) if self._slots
+                                         else (eng.lrts_collect, eng.shading_collect))
         if self._lrts.any():
-            need = self._bounds["lrts"] + (B * min(int(self.max_slots), max(P - 1, 0)) if slots else B)
+            need = self._bounds["lrts"] + (B * min(int(self.max_slots), max(P - 1, 0)) if self._slots else B)
             st = self._grow("lrts", need, eng.new_lrts_samples)
-            if slots:
-                eng.lrts_collect_slots(inp, out, st)
-            else:
-                eng.lrts_collect(inp, out, st)
+            lrts_collect(inp, out, st)
             self._bounds["lrts"] = need
         if self._shading_rec.any():
             need = self._bounds["shading"] + B * P
             learning = bool(self._learning.any())
             st = self._grow("shading", need, lambda cap: eng.new_shading_samples(cap, learning=learning))
-            if slots:
-                eng.shading_collect_slots(inp, out, st, first_auction=first_auction)
-            else:
-                eng.shading_collect(inp, out, st, first_auction=first_auction)
+            shading_collect(inp, out, st, first_auction=first_auction)
             self._bounds["shading"] = need
 
     def _update_agent(self, index, iteration):

@@ -51,7 +51,10 @@ def draw_rounds(rng, B, num_agents, num_participants, embedding_size, embedding_
 
 def _draw_slot_uniforms(rng, n, num_participants, max_slots):
     """The doubles rng.binomial(1, CTRs[winners]) consumes: min(n, P), NaN-padded to min(max_slots, P)."""
-    us = np.full(min(max_slots, num_participants), np.nan)
+    rows = min(max_slots, num_participants)
+    if rows == 1:  # then n >= 1 = rows: one double, as draw_round's
+        return np.array([rng.random()])
+    us = np.full(rows, np.nan)
     for k in range(min(n, num_participants)):
         us[k] = rng.random()
     return us
@@ -114,17 +117,12 @@ def _native_draws(rng, B, num_agents, num_participants, embedding_size, embeddin
     import ctypes
 
     from . import _lib
-    bg = rng.bit_generator
-    st = bg.state
-    if st.get("bit_generator") != "PCG64":
-        raise NotImplementedError("ag_replay_draw restates numpy's PCG64 only")
-    s, inc = int(st["state"]["state"]), int(st["state"]["inc"])
-    c = _lib.AgPcg64State(s >> 64, s & M64, inc >> 64, inc & M64, int(st["has_uint32"]), int(st["uinteger"]))
+    st, c = _pcg_in(rng)
     B, N, P, E = int(B), int(num_agents), int(num_participants), int(embedding_size)
     o = out or {}
     ctx = o.get("ctx") if o.get("ctx") is not None else np.empty((E, B))
     part = o.get("part") if o.get("part") is not None else np.empty((P, B), np.int32)
-    u = o.get("u") if o.get("u") is not None else np.empty(B)
+    u = None if slots else o.get("u") if o.get("u") is not None else np.empty(B)  # slots: u_slots' row 0
     g = None
     sh = pg = gs = None
     if shading is not None:
@@ -132,8 +130,8 @@ def _native_draws(rng, B, num_agents, num_participants, embedding_size, embeddin
         sh = np.array([x is not None for x in shading], np.uint8)
         pg = np.array([x[0] if x is not None else 0.0 for x in shading], np.float64)
         gs = np.array([x[1] if x is not None else 1.0 for x in shading], np.float64)
-    for a in (ctx, part, u) + ((g,) if g is not None else ()):
-        if not a.flags.c_contiguous:
+    for a in (ctx, part, u, g):
+        if a is not None and not a.flags.c_contiguous:
             raise ValueError("replay arrays must be C-contiguous")
     ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
     L = _lib.load()
@@ -147,11 +145,7 @@ def _native_draws(rng, B, num_agents, num_participants, embedding_size, embeddin
     else:
         _lib.check(L.ag_replay_draw(ctypes.byref(c), B, N, P, E, float(embedding_var), int(max_slots), ptr(sh),
                                     ptr(pg), ptr(gs), ptr(ctx), ptr(part), ptr(g), ptr(u)), "ag_replay_draw", L)
-    st["state"]["state"] = (int(c.state_hi) << 64) | int(c.state_lo)
-    st["state"]["inc"] = (int(c.inc_hi) << 64) | int(c.inc_lo)
-    st["has_uint32"] = int(c.has_uint32)
-    st["uinteger"] = int(c.uinteger)
-    bg.state = st
+    _pcg_out(rng, st, c)
     return ctx, part, u, g, ns, us
 
 

@@ -188,6 +188,22 @@ inline int ag_one_slot_only(const ag_ctx *c, const char *who) {
   return AG_OK;
 }
 
+// A caller's record store, as the collectors (ag_collect.hip) and the updates that read it take it.
+inline int ag_check_store(const ag_ctx *c, const ag_lrts_samples *s, const char *who) {
+  if (!c || !s) return ag_set_error(AG_ERR_INVALID, "%s: null argument", who);
+  AG_CHECK_STRUCT(s, who, "ag_lrts_samples");
+  if (!s->key || !s->x || !s->count || s->capacity < 0)
+    return ag_set_error(AG_ERR_INVALID, "%s: sample store needs key, x, count and capacity >= 0", who);
+  return AG_OK;
+}
+inline int ag_check_store(const ag_ctx *c, const ag_shading_samples *s, const char *who) {
+  if (!c || !s) return ag_set_error(AG_ERR_INVALID, "%s: null argument", who);
+  AG_CHECK_STRUCT(s, who, "ag_shading_samples");
+  if (!s->agent || !s->gamma || !s->utility || !s->count || s->capacity < 0)
+    return ag_set_error(AG_ERR_INVALID, "%s: sample store needs agent, gamma, utility, count, capacity", who);
+  return AG_OK;
+}
+
 struct AgDeviceGuard {
   int prev = -1;
   explicit AgDeviceGuard(int dev) {

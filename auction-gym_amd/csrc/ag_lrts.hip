@@ -1,12 +1,10 @@
 // ag_lrts.hip -- LR-TS allocator update on the GPU (Agent.update -> PyTorchLogistic-
 // RegressionAllocator.update, src/Agent.py:79-91, src/BidderAllocation.py:29-65,
-// src/Models.py:35-48), plus the won-sample collection that feeds it.
+// src/Models.py:35-48), on the won samples k_lrts_collect (ag_collect.hip) appended to a
+// caller-owned store: (agent, item, outcome, observed context + 1).
 //
-//  1. k_lrts_collect   after each ag_simulate: every auction won by an LR-TS agent
-//                      appends (agent, item, outcome, observed context + 1) to a
-//                      caller-owned store (one atomic per wave).
-//  2. bucket           histogram -> exclusive scan -> scatter: samples grouped by agent.
-//  3. k_lrts_train     one workgroup per agent, persistent over the epochs: forward, BCE +
+//  1. bucket           histogram -> exclusive scan -> scatter: samples grouped by agent.
+//  2. k_lrts_train     one workgroup per agent, persistent over the epochs: forward, BCE +
 //                      prior loss, gradient, Adam, ReduceLROnPlateau and the early stop all
 //                      on the device (no host round trip per epoch), then the Laplace
 //                      update of q and prev_m = m.
@@ -58,46 +56,7 @@ __device__ __forceinline__ int64_t wave_sum(int64_t v) {
 }
 
 // ---------------------------------------------------------------------------------------
-// 1. collection: Agent.update's won_mask (src/Agent.py:90) over one simulated batch
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kLrThreads) void k_lrts_collect(
-    int64_t B, int P, int OE, const double *__restrict__ ctx, const int32_t *__restrict__ part,
-    const int32_t *__restrict__ winner, const int32_t *__restrict__ item, const uint8_t *__restrict__ outcome,
-    const uint32_t *__restrict__ winner_outcome, const int32_t *__restrict__ akind, uint32_t *__restrict__ key,
-    float *__restrict__ x, int64_t cap, unsigned long long *__restrict__ count) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t base = (int64_t)blockIdx.x * kLrThreads; base < B; base += (int64_t)gridDim.x * kLrThreads) {
-    const int64_t i = base + threadIdx.x;
-    bool take = false;
-    uint32_t k = 0;
-    if (i < B && P >= 2) {  // P == 1: nobody is charged, no record is won (src/Auction.py:68)
-      // winner and outcome from their arrays, or from the ABI 17 packed word
-      const uint32_t wo = winner ? 0u : winner_outcome[i];
-      const int w = winner ? winner[i] : (int)(wo & 0x7fffffffu);
-      const int a = part[(size_t)w * B + i];
-      if (akind[a] == AG_ALLOCATOR_LRTS) {
-        take = true;
-        const bool oc = outcome ? outcome[i] != 0 : (wo >> 31) != 0;
-        k = ((uint32_t)a << 16) | ((uint32_t)item[(size_t)w * B + i] << 1) | (oc ? 1u : 0u);
-      }
-    }
-    const uint64_t ballot = __ballot(take);
-    if (ballot == 0) continue;
-    unsigned long long first = 0;
-    const int leader = __ffsll((unsigned long long)ballot) - 1;
-    if (lane == leader) first = atomicAdd(count, (unsigned long long)__popcll(ballot));
-    first = __shfl(first, leader, 64);
-    if (!take) continue;
-    const int64_t slot = (int64_t)first + __popcll(ballot & ((1ull << lane) - 1));
-    if (slot >= cap) continue;  // overflow: reported by ag_lrts_update
-    key[slot] = k;
-    for (int d = 0; d < OE; ++d) x[(size_t)d * cap + slot] = (float)ctx[(size_t)d * B + i];
-    x[(size_t)OE * cap + slot] = 1.0f;
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// 2. bucket by agent
+// 1. bucket by agent
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kLrThreads) void k_lrts_hist(const uint32_t *__restrict__ key, int64_t n, int N,
                                                           int64_t *__restrict__ counts) {
@@ -158,7 +117,7 @@ __global__ __launch_bounds__(kLrThreads) void k_lrts_scatter(const uint32_t *__r
 }
 
 // ---------------------------------------------------------------------------------------
-// 3. training: up to kLrCache * 256 samples per workgroup, several workgroups per agent
+// 2. training: up to kLrCache * 256 samples per workgroup, several workgroups per agent
 // ---------------------------------------------------------------------------------------
 struct LrSample {
   float x[AG_LRTS_MAX_DO];
@@ -405,7 +364,7 @@ __global__ __launch_bounds__(kLrThreads) void k_lrts_train(
 }
 
 // ---------------------------------------------------------------------------------------
-// 4. resumable / record-parallel training (ag_lrts_rp_*): the same fit as k_lrts_train, one
+// 3. resumable / record-parallel training (ag_lrts_rp_*): the same fit as k_lrts_train, one
 //    launch per epoch, each agent's state (m, Adam moments, scheduler, loss history, phase) in
 //    HBM between launches. Launch k steps the state with the totals of launch k - 1 (this
 //    rank's workgroups summed up the agent's combining tree without waiting, then -- G ranks --
@@ -607,14 +566,6 @@ TrainKernel pick_train(int Do) {
 
 int grid_over(int64_t n) { return agtrain::grid_over(n, kLrThreads); }
 
-int check_store(const ag_ctx *c, const ag_lrts_samples *s, const char *who) {
-  if (!c || !s) return ag_set_error(AG_ERR_INVALID, "%s: null argument", who);
-  AG_CHECK_STRUCT(s, who, "ag_lrts_samples");
-  if (!s->key || !s->x || !s->count || s->capacity < 0)
-    return ag_set_error(AG_ERR_INVALID, "%s: sample store needs key, x, count and capacity >= 0", who);
-  return AG_OK;
-}
-
 }  // namespace
 
 void ag_lrts_release(ag_ctx *c) {
@@ -633,32 +584,6 @@ void ag_lrts_release(ag_ctx *c) {
 }
 
 extern "C" {
-
-int ag_lrts_collect(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch_out *out_arg,
-                    const ag_lrts_samples *s, void *stream) {
-  if (int rc = ag_one_slot_only(c, "ag_lrts_collect")) return rc;
-  if (int rc = check_store(c, s, "ag_lrts_collect")) return rc;
-  if (!in || !out_arg) return ag_set_error(AG_ERR_INVALID, "ag_lrts_collect: null argument");
-  AG_CHECK_STRUCT(in, "ag_lrts_collect", "ag_batch_in");
-  ag_batch_out outv;
-  AG_READ_OUT(out_arg, outv, "ag_lrts_collect");
-  const ag_batch_out *out = &outv;
-  if (B < 0) return ag_set_error(AG_ERR_INVALID, "ag_lrts_collect: B < 0");
-  if (B == 0 || !c->has_lrts) return AG_OK;
-  if (c->shape.num_agents > 65536 || c->shape.num_items > 32768)
-    return ag_set_error(AG_ERR_UNSUPPORTED, "ag_lrts_collect: sample keys hold N <= 65536, K <= 32768");
-  if (!in->ctx || !in->part || !out->item || !((out->winner && out->outcome) || out->winner_outcome))
-    return ag_set_error(AG_ERR_INVALID, "ag_lrts_collect: needs in.ctx, in.part, out.item and out.winner + "
-                                        "out.outcome (or out.winner_outcome)");
-  AgDeviceGuard g(c->device);
-  hipLaunchKernelGGL(k_lrts_collect, dim3(grid_over(B)), dim3(kLrThreads), 0, (hipStream_t)stream, B,
-                     c->shape.num_participants, c->shape.obs_embedding_size, in->ctx, in->part,
-                     out->winner && out->outcome ? out->winner : nullptr, out->item,
-                     out->winner && out->outcome ? out->outcome : nullptr, out->winner_outcome, c->d_akind, s->key, s->x, s->capacity,
-                     (unsigned long long *)s->count);
-  AG_HIP(hipGetLastError());
-  return AG_OK;
-}
 
 // The won samples of a store bucketed by agent into the workspace (w.key, w.x with stride
 // w.cap; w.offsets [N + 1]): histogram -> exclusive scan -> scatter. Shared by ag_lrts_update
@@ -709,7 +634,7 @@ static int bucket_samples(ag_ctx *c, const ag_lrts_samples *s, hipStream_t st, c
 }
 
 int ag_lrts_update(ag_ctx *c, const ag_lrts_samples *s, int32_t *epochs, float *loss_trace, void *stream) {
-  if (int rc = check_store(c, s, "ag_lrts_update")) return rc;
+  if (int rc = ag_check_store(c, s, "ag_lrts_update")) return rc;
   if (!c->has_lrts) return AG_OK;
   if (!c->lrts_loaded) return ag_set_error(AG_ERR_STATE, "ag_lrts_update: ag_load_lrts not called");
   const int N = c->shape.num_agents, K = c->shape.num_items, Do = c->shape.obs_embedding_size + 1;
@@ -773,7 +698,7 @@ int ag_lrts_update(ag_ctx *c, const ag_lrts_samples *s, int32_t *epochs, float *
 // ---- resumable / record-parallel LR-TS training (k_lrts_epoch) ----
 int ag_lrts_rp_begin(ag_ctx *c, const ag_lrts_samples *s, const int32_t *agents, const int64_t *samples_total,
                      int64_t *totals, void *stream) {
-  if (int rc = check_store(c, s, "ag_lrts_rp_begin")) return rc;
+  if (int rc = ag_check_store(c, s, "ag_lrts_rp_begin")) return rc;
   if (!totals) return ag_set_error(AG_ERR_INVALID, "ag_lrts_rp_begin: null totals");
   if (!c->lrts_loaded) return ag_set_error(AG_ERR_STATE, "ag_lrts_rp_begin: ag_load_lrts not called");
   const int N = c->shape.num_agents, K = c->shape.num_items, Do = c->shape.obs_embedding_size + 1;

@@ -1,10 +1,10 @@
 // ag_shading.hip -- shading bidders' per-iteration update on the GPU:
 // EmpiricalShadedBidder.update (src/Agent.py:79-94 -> src/Bidder.py:60-147).
 //
-//  1. k_shading_collect  after each ag_simulate: every participation of a shading bidder
-//                        appends (agent, gamma, net utility) to a caller-owned store
-//                        (the update's `gammas` and `utilities`).
-//  2. k_empirical_update one workgroup per EmpiricalShadedBidder agent: min / max of its
+// on the (agent, gamma, net utility) records k_shading_collect (ag_collect.hip) appended to a
+// caller-owned store: the update's `gammas` and `utilities`.
+//
+//     k_empirical_update one workgroup per EmpiricalShadedBidder agent: min / max of its
 //                        gammas, the reference's bucket grid (Python floor division,
 //                        numpy.linspace edges), per-bucket counts and EXACT fixed-point sums
 //                        of u and (u - mean)^2 (LDS integer atomics: order-free), the lower
@@ -24,50 +24,6 @@ constexpr int kShThreads = 256;
 constexpr int kMaxBuckets = 1024;  // gammas of EmpiricalShadedBidder are in [0, 1]: <= 200
 constexpr double kFx = 0x1p40;
 constexpr int64_t kLo24 = (int64_t(1) << 24) - 1;
-
-__global__ __launch_bounds__(kShThreads) void k_shading_collect(
-    int64_t first, int64_t B, int P, int K, const int32_t *__restrict__ part, ag_batch_out out,
-    const int32_t *__restrict__ bkind, const double *__restrict__ values, ag_shading_samples st,
-    unsigned long long *__restrict__ count) {
-  const int lane = threadIdx.x & 63;
-  const bool charged = P >= 2;  // P == 1: nobody is charged (src/Auction.py:68)
-  for (int64_t base = (int64_t)blockIdx.x * kShThreads; base < B; base += (int64_t)gridDim.x * kShThreads) {
-    const int64_t i = base + threadIdx.x;
-    const bool live = i < B;
-    // winner and outcome from their arrays, or from the ABI 17 packed word
-    const uint32_t wo = (live && !out.winner) ? out.winner_outcome[i] : 0u;
-    const int w = live ? (out.winner ? out.winner[i] : (int)(wo & 0x7fffffffu)) : -1;
-    for (int s = 0; s < P; ++s) {
-      int a = -1;
-      bool take = false;
-      if (live) {
-        a = part[(size_t)s * B + i];
-        take = bkind[a] != AG_BIDDER_TRUTHFUL;  // Empirical, ValueLearning, PolicyLearning, DR
-      }
-      const uint64_t ballot = __ballot(take);
-      if (ballot == 0) continue;
-      unsigned long long base_slot = 0;
-      const int leader = __ffsll((unsigned long long)ballot) - 1;
-      if (lane == leader) base_slot = atomicAdd(count, (unsigned long long)__popcll(ballot));
-      base_slot = __shfl(base_slot, leader, 64);
-      if (!take) continue;
-      const int64_t slot = (int64_t)base_slot + __popcll(ballot & ((1ull << lane) - 1));
-      if (slot >= st.capacity) continue;  // overflow: reported by the update
-      const size_t o = (size_t)s * B + i;
-      const bool won = charged && s == w;
-      const double v = values[(size_t)a * K + out.item[o]];
-      st.agent[slot] = a;
-      st.gamma[slot] = out.gamma[o];
-      const bool oc = out.winner ? out.outcome[i] != 0 : (wo >> 31) != 0;
-      st.utility[slot] = won ? v * (oc ? 1.0 : 0.0) - out.price[i] : 0.0;  // src/Bidder.py:62-63
-      if (st.ctr) st.ctr[slot] = out.est_ctr[o];
-      if (st.value) st.value[slot] = v;
-      if (st.propensity) st.propensity[slot] = out.propensity[o];
-      if (st.won) st.won[slot] = won ? 1 : 0;
-      if (st.order) st.order[slot] = (uint64_t)(first + i) * (uint64_t)P + (uint64_t)s;
-    }
-  }
-}
 
 __device__ __forceinline__ double py_floordiv(double vx, double wx) {  // CPython float //
   const double mod = fmod(vx, wx);
@@ -221,49 +177,9 @@ __global__ __launch_bounds__(kShThreads) void k_empirical_update(
   }
 }
 
-int grid_over(int64_t n) {
-  int64_t g = (n + kShThreads - 1) / kShThreads;
-  if (g > 4096) g = 4096;
-  return (int)(g < 1 ? 1 : g);
-}
-
-int check_store(const ag_ctx *c, const ag_shading_samples *s, const char *who) {
-  if (!c || !s) return ag_set_error(AG_ERR_INVALID, "%s: null argument", who);
-  AG_CHECK_STRUCT(s, who, "ag_shading_samples");
-  if (!s->agent || !s->gamma || !s->utility || !s->count || s->capacity < 0)
-    return ag_set_error(AG_ERR_INVALID, "%s: sample store needs agent, gamma, utility, count, capacity", who);
-  return AG_OK;
-}
-
 }  // namespace
 
 extern "C" {
-
-int ag_shading_collect(ag_ctx *c, int64_t first, int64_t B, const ag_batch_in *in, const ag_batch_out *out_arg,
-                       const ag_shading_samples *s, void *stream) {
-  if (int rc = ag_one_slot_only(c, "ag_shading_collect")) return rc;
-  if (int rc = check_store(c, s, "ag_shading_collect")) return rc;
-  if (!in || !out_arg) return ag_set_error(AG_ERR_INVALID, "ag_shading_collect: null argument");
-  AG_CHECK_STRUCT(in, "ag_shading_collect", "ag_batch_in");
-  ag_batch_out outv;
-  AG_READ_OUT(out_arg, outv, "ag_shading_collect");
-  if (!(outv.winner && outv.outcome)) outv.winner = nullptr;  // then the packed word is read
-  const ag_batch_out *out = &outv;
-  if (B < 0) return ag_set_error(AG_ERR_INVALID, "ag_shading_collect: B < 0");
-  if (B == 0 || !c->has_shading) return AG_OK;
-  if (!in->part || !(out->winner || out->winner_outcome) || !out->item || !out->price || !out->gamma)
-    return ag_set_error(AG_ERR_INVALID, "ag_shading_collect: needs in.part, out.winner + out.outcome (or "
-                                        "out.winner_outcome), out.item, out.price, out.gamma");
-  if ((s->ctr && !out->est_ctr) || (s->propensity && !out->propensity))
-    return ag_set_error(AG_ERR_INVALID, "ag_shading_collect: the store's ctr / propensity need "
-                                        "out.est_ctr / out.propensity");
-  AgDeviceGuard g(c->device);
-  hipLaunchKernelGGL(k_shading_collect, dim3(grid_over(B)), dim3(kShThreads), 0, (hipStream_t)stream, first, B,
-                     c->shape.num_participants, c->shape.num_items, in->part, *out, c->d_bkind, c->d_values, *s,
-                     (unsigned long long *)s->count);
-  AG_HIP(hipGetLastError());
-  return AG_OK;
-}
 
 int ag_empirical_update(ag_ctx *c, const ag_shading_samples *s, double *prev_gamma, void *stream) {
   return ag_empirical_update_agents(c, s, nullptr, prev_gamma, stream);
@@ -271,7 +187,7 @@ int ag_empirical_update(ag_ctx *c, const ag_shading_samples *s, double *prev_gam
 
 int ag_empirical_update_agents(ag_ctx *c, const ag_shading_samples *s, const int32_t *agents, double *prev_gamma,
                                void *stream) {
-  if (int rc = check_store(c, s, "ag_empirical_update")) return rc;
+  if (int rc = ag_check_store(c, s, "ag_empirical_update")) return rc;
   const int N = c->shape.num_agents;
   AgDeviceGuard g(c->device);
   hipStream_t st = (hipStream_t)stream;

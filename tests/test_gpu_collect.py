@@ -1,7 +1,7 @@
 """The record collectors and the EmpiricalShadedBidder update at their edges.
 
-k_shading_collect (csrc/ag_shading.hip) writes every record the learning bidders and the
-EmpiricalShadedBidder update train on, k_lrts_collect (csrc/ag_lrts.hip) every sample the LR-TS
+k_shading_collect (csrc/ag_collect.hip) writes every record the learning bidders and the
+EmpiricalShadedBidder update train on, k_lrts_collect (the same file) every sample the LR-TS
 allocators train on. Both are pure functions of the arrays they are handed, so the reference here
 is a plain numpy statement of include/auctiongym.h's description on host copies of exactly those
 arrays (expected_records, expected_lrts_samples): every field of every record, bit for bit, the
@@ -10,7 +10,8 @@ count exact. The statements themselves are pinned without a GPU: the reference's
 the oracle's replay of the captures they were logged from.
 
 Covered: P = 1 (nobody is charged: won == 0), batch tails around a wave and a workgroup, P = 8 and
-the runtime-P kernel's P = 12, waves whose ballot is empty or has one taker, the second grid-stride
+the runtime-P kernel's P = 12, waves with no taker or one, one lane owning all of its wave's
+records, a one-lane tail, the second grid-stride
 pass (B = 2^20 + 37; 4096 workgroups of 256 lanes cover 2^20), a 64-bit order, the minimal store,
 hand-made outputs in both layouts (the winner in the last slot, price above value, a won auction
 without a click, bit 31 of the packed word), a store that overflows (guard tails past `capacity`
@@ -458,6 +459,46 @@ def test_shading_collect_hand_made_outputs(gpu):
 
 
 @gpu_test
+def test_shading_collect_one_lane_owns_every_record_of_its_wave(gpu):
+    """Hand-made outputs, no simulate: P = 4, B = 130 (two full waves and a 2-lane tail). Only the
+    auction at lane 1 of each wave (1, 65, 129) has non-truthful bidders, and it has them in all four
+    slots: one lane owns its wave's four records and its neighbours none, the case a per-lane prefix
+    sum can get wrong. Both output layouts, first_auction = 11."""
+    import torch
+    from auctiongym_amd.engine import AuctionEngine
+    N, P, K, B = 8, 4, 12, 130
+    g = np.random.default_rng(64)
+    bk = np.array([1, 4, 3, 2, 0, 0, 0, 0], np.int32)
+    items, values = _catalogue(g, N, K, 5)
+    eng = AuctionEngine(N, P, K, 5, 4, 0, 1.0)
+    eng.set_agent_params(np.zeros(N, np.int32), bk, np.ones(N), np.full(N, 0.05))
+    eng.load_catalog(items, values)
+    owners = np.array([1, 65, 129])
+    part = np.tile(np.arange(4, 8, dtype=np.int32), (B, 1))
+    part[owners] = [(0, 1, 2, 3), (3, 2, 1, 0), (2, 0, 3, 1)]
+    out = dict(winner=g.integers(0, P, B).astype(np.int32), outcome=(g.random(B) < 0.5).astype(np.uint8),
+               price=g.uniform(0.1, 2.5, B), item=g.integers(0, K, (B, P)).astype(np.int32),
+               gamma=g.uniform(0, 1.2, (B, P)), est_ctr=g.random((B, P)), propensity=g.uniform(0.1, 9, (B, P)))
+    out["outcome"][owners] = 1, 0, 1
+    want = expected_records(part, out, bk, values, P, 11)
+    assert len(want["order"]) == 4 * len(owners) and int(want["won"].sum()) == len(owners)
+    assert sorted(set(int(o) // P - 11 for o in want["order"])) == list(owners)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(eng.device)  # noqa: E731
+    inp = {"part": up(part.T), "u": up(np.zeros(B))}
+    dev = {k: up(v.T if v.ndim == 2 else v) for k, v in out.items()}
+    word = (out["winner"].astype(np.uint32) | (out["outcome"].astype(np.uint32) << 31)).view(np.int32)
+    packed = {k: v for k, v in dev.items() if k not in ("winner", "outcome")}
+    packed["winner_outcome"] = up(word)
+    for name, o in (("fields", dev), ("packed", packed)):
+        st = eng.new_shading_samples(P * B, learning=True)
+        eng.shading_collect(inp, o, st, first_auction=11)
+        torch.cuda.synchronize()
+        assert int(st["count"].item()) == 4 * len(owners), name
+        _assert_records(_records(st), want, name)
+    eng.close()
+
+
+@gpu_test
 def test_shading_collect_overflow_stays_inside_the_store(gpu):
     """A store 37 records too small, every field with a guard tail of sentinels right behind
     `capacity`: count still counts every record, the store holds `capacity` distinct records of the
@@ -548,6 +589,26 @@ def test_lrts_collect_p1_collects_nothing(gpu):
     torch.cuda.synchronize()
     assert int(st["count"].item()) == 0
     assert len(expected_lrts_samples(ctx, part, _host_out(out), np.ones(4, np.int32), 4, 1)[0]) == 0
+    eng.close()
+
+
+@gpu_test
+def test_lrts_collect_one_wave_and_one_lane(gpu):
+    """B = 65 at P = 2, every agent an LR-TS allocator: one full wave and a 1-lane tail, every
+    auction a sample."""
+    import torch
+    ak = np.ones(4, np.int32)
+    eng, g = _lrts_population(4, 2, ak, 73)
+    ctx, part, u = _rounds(g, 4, 2, 5, 65)
+    inp = _upload(eng, ctx, part, u)
+    out = eng.alloc_outputs(65)
+    eng.simulate(inp, out)
+    st = eng.new_lrts_samples(65)
+    eng.lrts_collect(inp, out, st)
+    torch.cuda.synchronize()
+    key, x = expected_lrts_samples(ctx, part, _host_out(out), ak, 4, 2)
+    assert int(st["count"].item()) == len(key) == 65
+    assert np.array_equal(_lrts_store_rows(st), _lrts_rows(key, x))
     eng.close()
 
 

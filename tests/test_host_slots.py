@@ -134,6 +134,73 @@ def test_one_slot_draw_functions_are_unchanged(slots):
     assert c.bit_generator.state == b.bit_generator.state
 
 
+def _same(x, y):
+    if x is None or y is None:
+        return x is None and y is None
+    return np.array_equal(np.asarray(x), np.asarray(y), equal_nan=True)
+
+
+@pytest.mark.parametrize("P", [1, 3])
+@pytest.mark.parametrize("pop", ["plain", "shading", "ts_policy"])
+def test_slot_draws_at_one_slot_are_the_one_slot_draws(pop, P):
+    """At max_slots = 1 the four *_slots draw functions give their one-slot counterparts' numbers
+    (u_slots[0] == u, num_slots == 1) and leave numpy's generator, and torch's, in the same state:
+    what lets Auction draw every round, one-slot ones too, through the *_slots functions."""
+    from auctiongym_amd import replay as R
+    N, E, B = 6, 5, 200
+    shading = [None] * N
+    ts = [None] * N
+    policy = None
+    if pop == "shading":
+        shading = [(0.9 + 0.01 * a, 0.05) if a % 2 else None for a in range(N)]
+    elif pop == "ts_policy":
+        gen = torch.Generator().manual_seed(5)
+        ts = [_TsModel(torch.rand(12, 5, generator=gen) * 3 + 0.05) if a % 3 != 1 else None for a in range(N)]
+        policy = [a % 2 == 0 for a in range(N)]
+        shading = [(1.0 + 0.1 * a, 0.05) if a % 4 == 1 else None for a in range(N)]
+
+    def both(one, slots):
+        """Run the pair from equal numpy and torch states; both states must end equal."""
+        a, b = _entered(41)
+        torch.manual_seed(7)
+        x = one(a)
+        t_one = torch.get_rng_state()
+        torch.manual_seed(7)
+        y = slots(b)
+        assert torch.equal(torch.get_rng_state(), t_one)
+        assert a.bit_generator.state == b.bit_generator.state and a.random() == b.random()
+        return x, y
+
+    # the per-round Python draws
+    def rounds_one(g):
+        return [R.draw_round_population(g, N, P, E, 1.0, shading, ts, 1, policy, None) for _ in range(B)]
+
+    def rounds_slots(g):
+        return [R.draw_round_population_slots(g, N, P, E, 1.0, shading, ts, 1, policy, None) for _ in range(B)]
+    for (ctx, part, gr, u, nz, ee, grid), (c2, p2, g2, us, n2, e2, grid2, n) in zip(*both(rounds_one, rounds_slots)):
+        assert n == 1 and us.shape == (1,) and us[0] == u
+        assert all(_same(v, w) for v, w in ((ctx, c2), (part, p2), (gr, g2), (nz, n2), (ee, e2), (grid, grid2)))
+    # the native population draws
+    sh = shading if pop != "plain" else None
+    (ctx, part, gr, u, nz, ee, grid), y = both(
+        lambda g: R.draw_rounds_native_population(g, B, N, P, E, 1.0, sh, ts, 1, policy, None),
+        lambda g: R.draw_rounds_native_population_slots(g, B, N, P, E, 1.0, sh, ts, 1, policy, None))
+    assert all(_same(v, w) for v, w in zip((ctx, part, gr, u, nz, ee, grid), y[:7]))
+    assert np.array_equal(y[7], np.ones(B, np.int32)) and y[8].shape == (1, B) and np.array_equal(y[8][0], u)
+    if pop == "ts_policy":
+        return  # the functions below make numpy's draws only
+    (ctx, part, u, gr), (c2, p2, g2, ns, us) = both(
+        lambda g: R.draw_rounds_native(g, B, N, P, E, 1.0, 1, sh),
+        lambda g: R.draw_rounds_native_slots(g, B, N, P, E, 1.0, 1, sh))
+    assert _same(ctx, c2) and _same(part, p2) and _same(gr, g2)
+    assert np.array_equal(ns, np.ones(B, np.int32)) and us.shape == (1, B) and np.array_equal(us[0], u)
+    if pop == "plain":
+        for (ctx, part, u), (c2, p2, n, us) in zip(*both(
+                lambda g: [R.draw_round(g, N, P, E, 1.0, 1) for _ in range(B)],
+                lambda g: [R.draw_round_slots(g, N, P, E, 1.0, 1) for _ in range(B)])):
+            assert n == 1 and us.shape == (1,) and us[0] == u and _same(ctx, c2) and _same(part, p2)
+
+
 def test_slot_draw_errors():
     from auctiongym_amd.replay import draw_rounds_native_slots
     with pytest.raises(ValueError, match="larger sample than population"):
