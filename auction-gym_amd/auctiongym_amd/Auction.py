@@ -25,6 +25,8 @@ draws are draw_round_population's with the slot count kept and one click double 
 (replay.draw_round_population_slots), and the records Agent.update trains on are collected per
 launch by ag_lrts_collect_slots / ag_shading_collect_slots (one LR-TS sample per filled slot an LR-TS
 agent won; utilities on the round's logged price); the updates themselves are slot-agnostic.
+simulate_synthetic draws the slot counts and click uniforms on the device as well
+(ag_generate_slots) and runs the same pipeline.
 Without the flag such an Auction is refused, as it was before those collectors existed; Agent(memory
 > 0) with several slots is refused either way.
 """
@@ -310,10 +312,9 @@ class Auction:
             self._run(self._device_inputs(Draws(ctx, part, ns, us, g, noise, eps, grid)))
 
     def simulate_synthetic(self, B, seed, first_auction=0):
-        """B rounds with on-device Philox inputs (throughput mode; parity via the oracle)."""
-        if self._slots:
-            raise NotImplementedError("synthetic inputs for multi-slot rounds are not built (ag_generate draws "
-                                      "no slot counts)")
+        """B rounds with on-device Philox inputs (throughput mode; parity via the oracle). Several
+        slots: the slot counts and click uniforms drawn too (ag_generate_slots), then the same
+        pipeline as replayed multi-slot rounds -- logs kept, learners' records collected."""
         self._settle_lrts()
         self._flush()
         eng = self._engine
@@ -330,6 +331,8 @@ class Auction:
             inp["ts_noise"].mul_(pad.view(P, T, 1, 64).to(inp["ts_noise"].dtype))
         if "gamma_grid" in inp:
             eng.generate_search_grid(seed, first_auction, inp)
+        if self._slots:
+            eng.generate_slots(seed, first_auction, inp)
         self._run(inp)
 
     # ------------------------------------------------------------------ engine

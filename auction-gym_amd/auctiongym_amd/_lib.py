@@ -51,7 +51,7 @@ EXPORTS = ("ag_create", "ag_destroy", "ag_set_agent_kinds", "ag_set_agent_params
            "ag_lrts_rp_begin", "ag_lrts_rp_epoch", "ag_lrts_rp_poll", "ag_lrts_rp_end", "ag_empirical_update_agents",
            "ag_coop_selftest", "ag_div_selftest",
            "ag_simulate_slots", "ag_allocate_slots", "ag_replay_draw_slots", "ag_replay_draw_population_slots",
-           "ag_lrts_collect_slots", "ag_shading_collect_slots")
+           "ag_lrts_collect_slots", "ag_shading_collect_slots", "ag_generate_slots", "ag_simulate_slots_generated")
 ABI_VERSION = 17
 MAX_SLOTS = 8  # AG_MAX_SLOTS
 LEARNER_UNINITIALISED, LEARNER_POLICY, LEARNER_SEARCH = 0, 1, 2
@@ -190,6 +190,8 @@ def load(path=None):
         "ag_simulate_slots": (ctypes.c_int, [vp, i64, ctypes.POINTER(AgBatchIn), vp, vp,
                                              ctypes.POINTER(AgSlotsOut), vp, vp]),
         "ag_allocate_slots": (ctypes.c_int, [vp, vp, vp, i32, i64, vp, vp, vp, vp]),
+        "ag_generate_slots": (ctypes.c_int, [vp, u64, u64, i64, vp, vp, vp]),
+        "ag_simulate_slots_generated": (ctypes.c_int, [vp, u64, u64, i64, ctypes.POINTER(AgSlotsOut), vp, vp]),
         "ag_lrts_collect_slots": (ctypes.c_int, [vp, i64, ctypes.POINTER(AgBatchIn), ctypes.POINTER(AgSlotsOut),
                                                  ctypes.POINTER(AgLrtsSamples), vp]),
         "ag_shading_collect_slots": (ctypes.c_int, [vp, i64, i64, ctypes.POINTER(AgBatchIn),

@@ -300,6 +300,9 @@ class AuctionEngine:
         if getattr(self, "lrts", False) and getattr(self, "ts_sample", True):
             inp["ts_noise"] = torch.empty((self.P, (B + 63) // 64, self.K * (self.OE + 1), 64),
                                           dtype=torch.float32, device=d)
+        if self.max_slots > 1:  # several slots: what generate_slots fills and simulate_slots reads
+            inp["num_slots"] = torch.empty((B,), dtype=torch.int32, device=d)
+            inp["u_slots"] = torch.empty((self.max_slots, B), dtype=torch.float64, device=d)
         return inp
 
     @staticmethod
@@ -442,6 +445,33 @@ class AuctionEngine:
         B = inputs["u"].shape[0]
         self._check(self.L.ag_generate(self._h, int(seed), int(first_auction), B, _ptr(inputs["ctx"]),
                                  _ptr(inputs["part"]), _ptr(inputs["u"]), _stream()), "ag_generate")
+
+    def generate_slots(self, seed, first_auction, inputs):
+        """Synthetic slot counts into inputs["num_slots"] (int32 [B], 1..max_slots) and click
+        uniforms into inputs["u_slots"] (float64 [max_slots][B], row 0 = generate's u) of auctions
+        [first_auction, first_auction + B) (ag_generate_slots); either may be absent."""
+        ns, us = inputs.get("num_slots"), inputs.get("u_slots")
+        if ns is None and us is None:
+            raise ValueError("generate_slots needs inputs['num_slots'] or inputs['u_slots']")
+        B = ns.shape[0] if ns is not None else us.shape[1]
+        if ns is not None and (ns.dtype != torch.int32 or ns.shape != (B,) or not ns.is_contiguous()
+                               or ns.device != self.device):
+            raise ValueError(f"num_slots must be a contiguous int32 [B] tensor on {self.device}")
+        if us is not None and (us.dtype != torch.float64 or us.shape != (self.max_slots, B)
+                               or not us.is_contiguous() or us.device != self.device):
+            raise ValueError(f"u_slots must be a contiguous float64 [max_slots][B] tensor on {self.device}")
+        self._check(self.L.ag_generate_slots(self._h, int(seed), int(first_auction), B, _ptr(ns), _ptr(us),
+                                             _stream()), "ag_generate_slots")
+
+    def simulate_slots_generated(self, seed, first_auction, outputs, counters=None):
+        """Generate mode for multi-slot rounds (ag_simulate_slots_generated): B = the last dimension
+        of the output arrays (alloc_slot_outputs) rounds whose inputs are drawn inside the kernel --
+        the same bits generate (+ generate_noise) and generate_slots write for (seed,
+        first_auction) -- so only the outputs touch HBM. P <= 16."""
+        B = _slots_batch({}, outputs)
+        so = _slots_out(outputs)
+        self._check(self.L.ag_simulate_slots_generated(self._h, int(seed), int(first_auction), B, ctypes.byref(so),
+                                                       _ptr(counters), _stream()), "ag_simulate_slots_generated")
 
     def generate_search_grid(self, seed, first_auction, inputs):
         """Synthetic ValueLearningBidder search grids into inputs["gamma_grid"] (ag_generate_search_grid)."""

@@ -152,7 +152,7 @@ struct ag_ctx {
   int32_t sim_kernel = AG_SIM_KERNEL_AUTO;  // AG_OPT_SIMULATE_KERNEL
   int32_t grid_per_cu = 0;                  // AG_OPT_SIM_BLOCKS_PER_CU (0: as many as fit)
   int32_t block_threads = 0;                // AG_OPT_SIM_BLOCK_THREADS (0: auto)
-  int32_t resident_slots[3][8] = {};        // resident blocks of the multi-slot builds [SM 2, 4, 8][general][screened][counters]
+  int32_t resident_slots[3][16] = {};       // resident blocks of the multi-slot builds [SM 2, 4, 8][generate mode][general][screened][counters]
   int32_t resident_ora[8] = {};             // resident blocks of k_oracle [specialised][generate][counters]
   // general populations (anything beyond OracleAllocator + TruthfulBidder)
   bool general = false, has_lrts = false, has_shading = false, lrts_loaded = false;

@@ -186,6 +186,35 @@ __global__ __launch_bounds__(kThreads) void k_generate(uint64_t seed, uint64_t f
   }
 }
 
+// The draws of multi-slot rounds (ag_generate_slots; ag_philox.h gen_num_slots / gen_u_slot, which
+// the SLOTS builds' generate mode draws in place): the slot count and the S = max_slots doubles
+// the round's binomial may consume, row 0 the auction's u. One lane per auction, coalesced rows.
+__global__ __launch_bounds__(kThreads) void k_generate_slots(uint64_t seed, uint64_t first, int64_t B, int S,
+                                                            int32_t *num_slots, double *u_slots) {
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < B;
+       i += (int64_t)gridDim.x * kThreads) {
+    const uint64_t idx = first + (uint64_t)i;
+    const uint32_t c0 = (uint32_t)idx, c1 = (uint32_t)(idx >> 32);
+    uint32_t w[4];
+    if (u_slots) {
+      philox(c0, c1, 0, gen_stream(kDrawUniform), k0, k1, w);
+      u_slots[i] = (double)((((uint64_t)w[0] << 32) | w[1]) >> 11) * 0x1p-53;
+    }
+    gen_slots_block(c0, c1, 0, k0, k1, w);
+    if (num_slots) num_slots[i] = gen_num_slots(w, S);
+    if (u_slots) {
+#pragma unroll
+      for (int k = 1; k < AG_MAX_SLOTS; ++k) {
+        if (k < S) {
+          if (k >= 2 && (k & 1) == 0) gen_slots_block(c0, c1, (uint32_t)(k >> 1), k0, k1, w);
+          u_slots[(int64_t)k * B + i] = gen_u_slot(w, k);
+        }
+      }
+    }
+  }
+}
+
 // Synthetic per-participant noise (ag_philox.h gen_normals4 / gen_normal1 / gen_shading_raw,
 // which the general kernel's generate mode draws in place): shading bidders' gamma_raw =
 // prev_gamma + sigma * z (numpy normal(loc, scale)), LR-TS agents' ts_noise = z * (1 / sqrt(q))
@@ -494,12 +523,13 @@ int simulate_oracle(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch_
 // k_simulate over a batch (replay / HBM-resident inputs, or generate mode: gen, every input drawn
 // in the kernel from (seed, first + auction index) as ag_generate + ag_generate_noise draw them)
 // sl: multi-slot rounds (ag_simulate_slots) -- the SLOTS build holding the context's max_slots,
-// 256 lanes, the whole population kind by kind at run time (kGenAll) or Oracle + Truthful
-SimKernel pick_slots(int sm, int D, bool prune, int general) {
+// 256 lanes, the whole population kind by kind at run time (kGenAll) or Oracle + Truthful; with
+// gen (ag_simulate_slots_generated) the build's generate mode, sl->num_slots and sl->u unread
+SimKernel pick_slots(int sm, int D, bool prune, int general, bool gen) {
   switch (sm) {
-    case 2: return pick_slots_for<2>(D, prune, general);
-    case 4: return pick_slots_for<4>(D, prune, general);
-    case 8: return pick_slots_for<8>(D, prune, general);
+    case 2: return pick_slots_for<2>(D, prune, general, gen);
+    case 4: return pick_slots_for<4>(D, prune, general, gen);
+    case 8: return pick_slots_for<8>(D, prune, general, gen);
     default: return nullptr;
   }
 }
@@ -566,8 +596,12 @@ int simulate_general(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch
     bt = kMidThreads;
   const int genb = gen ? kGenGen : 0;  // generate mode: the shipped shape's GEN builds
   const int sm = sl ? slots_build(sl->max_slots) : 0;
-  SimKernel k = sl ? pick_slots(sm, D, prune, gmode)
+  SimKernel k = sl ? pick_slots(sm, D, prune, gmode, gen)
                    : pick_kernel(s.num_participants, D, prune, gmode | ship | genb, bt);
+  if (sl && !k && gen)
+    return ag_set_error(AG_ERR_UNSUPPORTED,
+                        "ag_simulate_slots_generated: supports E+1 in 2..8, general populations in the shipped "
+                        "shape only (E = 5, OE = 4; P=%d D=%d)", s.num_participants, D);
   if (sl && !k)
     return ag_set_error(AG_ERR_UNSUPPORTED, "ag_simulate_slots: supports E+1 in 2..8 (P=%d D=%d)",
                         s.num_participants, D);
@@ -600,8 +634,8 @@ int simulate_general(ag_ctx *c, int64_t B, const ag_batch_in *in, const ag_batch
   }
   // Persistent grid: exactly the blocks the device keeps resident (no partial last round),
   // each striding over bt-auction tiles.
-  int &res = sl ? c->resident_slots[sm == 2 ? 0 : (sm == 4 ? 1 : 2)][(c->general ? 4 : 0) + (prune ? 2 : 0) +
-                                                                    (prm.want_counters ? 1 : 0)]
+  int &res = sl ? c->resident_slots[sm == 2 ? 0 : (sm == 4 ? 1 : 2)][(gen ? 8 : 0) + (c->general ? 4 : 0) +
+                                                                    (prune ? 2 : 0) + (prm.want_counters ? 1 : 0)]
                 : c->resident[(gen ? 128 : 0) + (bt == kMidThreads ? 64 : 0) + (ship ? 32 : 0) +
                          (gmode == kGenTruthful ? 16 : 0) + (bt == kThreads ? 0 : 8) + (c->general ? 4 : 0) +
                          (prune ? 2 : 0) + (prm.want_counters ? 1 : 0)];
@@ -1049,6 +1083,48 @@ int ag_simulate_slots(ag_ctx *c, int64_t B, const ag_batch_in *in, const int32_t
   return simulate_general(c, B, in, &po, counters_fx, (hipStream_t)stream, false, 0, 0, &sl);
 }
 
+int ag_simulate_slots_generated(ag_ctx *c, uint64_t seed, uint64_t first, int64_t B, ag_slots_out *out,
+                                int64_t *counters_fx, void *stream) {
+  const char *who = "ag_simulate_slots_generated";
+  if (!c || !out) return ag_set_error(AG_ERR_INVALID, "%s: null argument", who);
+  AG_CHECK_STRUCT(out, who, "ag_slots_out");
+  const ag_shape &s = c->shape;
+  if (c->D > 8 || !c->can_simulate)
+    return ag_set_error(AG_ERR_UNSUPPORTED, "%s: supports E+1 in 2..8 and a catalogue that fits LDS (P=%d, D=%d, "
+                        "N=%d, K=%d)", who, s.num_participants, c->D, s.num_agents, s.num_items);
+  if (s.num_participants > kGenSlotsMaxP)  // the picks' LDS columns
+    return ag_set_error(AG_ERR_UNSUPPORTED, "%s: P <= %d (P=%d); ag_generate + ag_generate_slots + "
+                        "ag_simulate_slots serve P <= %d", who, kGenSlotsMaxP, s.num_participants, kGenMaxSlots);
+  if (c->general) {
+    if (c->vl_any_search)
+      return ag_set_error(AG_ERR_UNSUPPORTED, "%s: ValueLearningBidders bidding by search (their 128-point grids "
+                          "are not drawn in the kernel)", who);
+    if (c->D != 6 || s.obs_embedding_size + 1 != kShipDo)
+      return ag_set_error(AG_ERR_UNSUPPORTED, "%s: general populations in the shipped shape only (E = 5, OE = 4; "
+                          "E=%d OE=%d)", who, s.embedding_size, s.obs_embedding_size);
+    if (c->has_lrts && !c->lrts_loaded) return ag_set_error(AG_ERR_STATE, "%s: LR-TS agents need ag_load_lrts", who);
+  }
+  if (!c->catalog) return ag_set_error(AG_ERR_STATE, "%s: ag_load_catalog not called", who);
+  if (B < 0) return ag_set_error(AG_ERR_INVALID, "%s: B < 0", who);
+  if (B == 0) return AG_OK;
+  if (B * std::max(s.num_participants, s.num_slots) > INT32_MAX)
+    return ag_set_error(AG_ERR_UNSUPPORTED, "%s: B * max(P, max_slots) must be < 2^31 (32-bit SoA indexing); "
+                        "split the batch", who);
+  AgDeviceGuard g(c->device);
+  ag_batch_out po{};  // the per-participant arrays go through the kernel's ag_batch_out
+  po.struct_size = sizeof(ag_batch_out);
+  po.item = out->item;
+  po.bid = out->bid;
+  po.est_ctr = out->est_ctr;
+  po.true_ctr = out->true_ctr;
+  po.best_ev = out->best_ev;
+  po.gamma = out->gamma;
+  po.propensity = out->propensity;
+  const SlotsIo sl{nullptr, nullptr, s.num_slots, out->winner, out->price, out->second_price, out->outcome,
+                   out->log_price, out->num_filled, out->won_slot};
+  return simulate_general(c, B, nullptr, &po, counters_fx, (hipStream_t)stream, true, seed, first, &sl);
+}
+
 int ag_allocate_slots(ag_ctx *c, const double *bids, const int32_t *num_slots, int32_t max_slots, int64_t B,
                       int32_t *winner, double *price, double *second_price, void *stream) {
   if (!c || (!bids && B > 0)) return ag_set_error(AG_ERR_INVALID, "ag_allocate_slots: null argument");
@@ -1130,6 +1206,19 @@ int ag_generate(ag_ctx *c, uint64_t seed, uint64_t first, int64_t B, double *ctx
   hipLaunchKernelGGL(k_generate, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, seed, first, B,
                      c->shape.num_agents, c->shape.num_participants, c->shape.embedding_size,
                      c->shape.embedding_var, ctx_out, part_out, u_out);
+  AG_HIP(hipGetLastError());
+  return AG_OK;
+}
+
+int ag_generate_slots(ag_ctx *c, uint64_t seed, uint64_t first, int64_t B, int32_t *num_slots, double *u_slots,
+                      void *stream) {
+  if (!c) return ag_set_error(AG_ERR_INVALID, "ag_generate_slots: null argument");
+  if (B < 0) return ag_set_error(AG_ERR_INVALID, "ag_generate_slots: B < 0");
+  if (B == 0 || (!num_slots && !u_slots)) return AG_OK;
+  AgDeviceGuard g(c->device);
+  const int grid = grid_for(B, (int64_t)1 << 40);
+  hipLaunchKernelGGL(k_generate_slots, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, seed, first, B,
+                     c->shape.num_slots, num_slots, u_slots);
   AG_HIP(hipGetLastError());
   return AG_OK;
 }

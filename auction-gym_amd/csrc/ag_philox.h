@@ -40,9 +40,12 @@ __device__ __forceinline__ void philox(uint32_t c0, uint32_t c1, uint32_t c2, ui
 //   Thompson   4 + s (s < 12),   64 + s above  c / 4 of coefficient c             (<= 16 blocks)
 //   policy     16 + s (s < 12), 128 + s above  0
 //   grid       32 + s (s < 12), 192 + s above  j / 2 of grid point j              (64 blocks)
+//   slots      256                             0 (word 0: the slot count; words 2-3: u_slots[1]),
+//                                              k / 2 of u_slots[k], k = 2..7     (4 blocks)
 // Slots 0..11 have the streams they always had. The slots from 12 up once continued base + s,
 // into the next kind's streams (slot 12's Thompson block 0 was slot 0's policy draw); they now
-// have ranges of their own, 76..127, 140..191 and 204..255. The host refuses P > 64.
+// have ranges of their own, 76..127, 140..191 and 204..255. The host refuses P > 64. Stream 256,
+// the first above the grids', holds the draws of a multi-slot round (gen_num_slots, gen_u_slot).
 enum GenDraw : uint32_t {
   kDrawUniform,
   kDrawPicks,
@@ -50,10 +53,12 @@ enum GenDraw : uint32_t {
   kDrawShading,
   kDrawThompson,
   kDrawPolicy,
-  kDrawGrid
+  kDrawGrid,
+  kDrawSlots
 };
 constexpr int kGenWideSlot = 12, kGenMaxSlots = 64;
 __device__ __forceinline__ uint32_t gen_stream(GenDraw kind, int s = 0) {
+  if (kind == kDrawSlots) return 256u;
   if (kind <= kDrawShading) return (uint32_t)kind;
   const uint32_t k = (uint32_t)kind - kDrawThompson;  // 0, 1, 2
   const uint32_t base = k == 0 ? 4u : k == 1 ? 16u : 32u;
@@ -75,9 +80,11 @@ __device__ __forceinline__ float gen_normal_r(uint32_t a) {  // sqrt(-2 ln u1), 
   const float u1 = (float)(((double)a + 1.0) * 0x1p-32);
   return __builtin_sqrtf(-2.0f * 0.693147180559945309f * __builtin_amdgcn_logf(u1));
 }
-template <int MAXP, int MAXE>
-__device__ __forceinline__ void gen_auction(uint32_t k0, uint32_t k1, uint64_t idx, int N, int P, int E,
-                                            double scale, double (&x)[MAXE], int (&part)[MAXP], double &u) {
+// PART: where the picks go, indexed by participant slot -- a register array (gen_auction), or a
+// lane's column of LDS (the multi-slot generate mode, whose slot loops index it at run time).
+template <int MAXE, class PART>
+__device__ __forceinline__ void gen_auction_to(uint32_t k0, uint32_t k1, uint64_t idx, int N, int P, int E,
+                                               double scale, double (&x)[MAXE], PART &part, double &u) {
   const uint32_t c0 = (uint32_t)idx, c1 = (uint32_t)(idx >> 32);
   uint32_t w[4], v[4];
   philox(c0, c1, 0, gen_stream(kDrawUniform), k0, k1, w);
@@ -86,10 +93,12 @@ __device__ __forceinline__ void gen_auction(uint32_t k0, uint32_t k1, uint64_t i
     const int step = j - (N - P);
     uint32_t word;
     if (step < 2) {
-      word = w[2 + step];
+      word = step == 0 ? w[2] : w[3];
     } else {
-      if (((step - 2) & 3) == 0) philox(c0, c1, (uint32_t)((step - 2) >> 2), gen_stream(kDrawPicks), k0, k1, v);
-      word = v[(step - 2) & 3];
+      // (selects, not v[r]: with P a runtime value an indexed word array would live in scratch)
+      const int r = (step - 2) & 3;
+      if (r == 0) philox(c0, c1, (uint32_t)((step - 2) >> 2), gen_stream(kDrawPicks), k0, k1, v);
+      word = r == 0 ? v[0] : (r == 1 ? v[1] : (r == 2 ? v[2] : v[3]));
     }
     int pick = (int)(((uint64_t)word * (uint64_t)(j + 1)) >> 32);
     for (int q = 0; q < step; ++q)
@@ -106,6 +115,29 @@ __device__ __forceinline__ void gen_auction(uint32_t k0, uint32_t k1, uint64_t i
     x[2 * m] = 0.0 + scale * (double)(r * __builtin_amdgcn_cosf(t));
     if (2 * m + 1 < E) x[2 * m + 1] = 0.0 + scale * (double)(r * __builtin_amdgcn_sinf(t));
   }
+}
+template <int MAXP, int MAXE>
+__device__ __forceinline__ void gen_auction(uint32_t k0, uint32_t k1, uint64_t idx, int N, int P, int E,
+                                            double scale, double (&x)[MAXE], int (&part)[MAXP], double &u) {
+  gen_auction_to<MAXE>(k0, k1, idx, N, P, E, scale, x, part, u);
+}
+
+// The draws of a multi-slot round (ag_generate_slots; fused into k_simulate's SLOTS builds in
+// generate mode), stream 256. The slot count n = 1 + ((w0 * S) >> 32) in 1..S = max_slots, the
+// participant picks' multiply-shift, from word 0 of block 0 (rng.integers(1, max_slots + 1) of
+// src/Auction.py:30 in distribution); word 1 of that block is unused. The k-th double the
+// round's binomial consumes: k = 0 is the auction's u (stream 0); k = 1..7 the 53-bit uniform of
+// words 2 (k & 1), 2 (k & 1) + 1 of block k / 2 -- k = 1 shares block 0 with the count.
+// tests/gen_slots_reference.py states the same.
+__device__ __forceinline__ void gen_slots_block(uint32_t c0, uint32_t c1, uint32_t blk, uint32_t k0, uint32_t k1,
+                                                uint32_t (&w)[4]) {
+  philox(c0, c1, blk, gen_stream(kDrawSlots), k0, k1, w);
+}
+__device__ __forceinline__ int gen_num_slots(const uint32_t (&w)[4], int S) {
+  return 1 + (int)(((uint64_t)w[0] * (uint64_t)S) >> 32);
+}
+__device__ __forceinline__ double gen_u_slot(const uint32_t (&w)[4], int k) {  // w: block k / 2
+  return (double)((((uint64_t)w[2 * (k & 1)] << 32) | w[2 * (k & 1) + 1]) >> 11) * 0x1p-53;
 }
 
 // Synthetic per-participant draws (ag_generate_noise writes them; the general kernel's generate

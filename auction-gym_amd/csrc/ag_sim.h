@@ -30,6 +30,11 @@ namespace ag {
                                 // configs_2 0.212 -> 0.203 ms, configs_3 0.129 -> 0.121 ms in one
                                 // process (profiles/r03s11_ab_w4.log)
 #endif
+#ifndef AG_SLOTS_GEN_MIN_WAVES
+#define AG_SLOTS_GEN_MIN_WAVES 3  // the multi-slot general builds' generate mode: 168 VGPRs, 39-140 spilled;
+                                  // at 2 (202-231 VGPRs, none spilled) the mixed population at P = 3,
+                                  // max_slots = 3 ran 2.950 -> 3.143 ms
+#endif
 #ifndef AG_TB_WIDE_MIN_WAVES
 #define AG_TB_WIDE_MIN_WAVES 3  // ... at P >= 3 (streamed slots): 168 VGPRs, 2 spilled instead of 81;
                                 // configs_1 at P = 8 0.658 -> 0.558 ms (profiles/r04o_ab_c1p8_tb3.log)
@@ -91,6 +96,7 @@ constexpr int kMinGrid = 2048;             // 256 CUs x 8
 constexpr int kMaxSimGrid = 2048;          // partial-sum workspace (>= resident blocks)
 constexpr int kMaxP = 8;                   // per-lane slot registers (template range)
 constexpr int kMaxD = 16;
+constexpr int kGenSlotsMaxP = 16;          // multi-slot generate mode: participants per round (LDS pick columns)
 constexpr double kFxScale = 0x1p36;        // 2^AG_FX_FRAC_BITS
 constexpr double kMagic = 0x1.8p52;
 constexpr int64_t kLimbMask = (int64_t(1) << AG_FX_LIMB_BITS) - 1;
@@ -487,6 +493,20 @@ struct Lds {
 // generate mode: one auction's Philox counter (its global index) and key
 struct GenKey {
   uint32_t c0, c1, k0, k1;
+};
+
+// multi-slot generate mode: a lane's participants as a column of LDS, slot s at col[s * BT] (an
+// agent index fits 16 bits: a catalogue of 2^16 agents does not fit LDS). What gen_auction_to
+// writes its Floyd picks through.
+template <int BT>
+struct PickColumn {
+  uint16_t *col;
+  struct Ref {
+    uint16_t *p;
+    __device__ __forceinline__ operator int() const { return (int)*p; }
+    __device__ __forceinline__ void operator=(int v) const { *p = (uint16_t)v; }
+  };
+  __device__ __forceinline__ Ref operator[](int s) const { return Ref{col + s * BT}; }
 };
 
 // Where a slot's Thompson noise comes from: the HBM tiles (replay and HBM-resident synthetic
@@ -1058,10 +1078,15 @@ __device__ __forceinline__ void resolve(const Lds &T, int K, int mech, const dou
 // only the outputs touch HBM. Shipped-shape builds (DOS > 0) only.
 // SLOTS: 0, or the multi-slot build (ag_simulate_slots) for up to SLOTS slots per auction: a
 // branch beside the runtime-P one (P == 0), sharing its prologue, resolve_slot and the exact
-// counters' accumulate and write-out.
+// counters' accumulate and write-out. SLOTS with GEN (ag_simulate_slots_generated): the branch's
+// inputs drawn in place, the bits ag_generate (+ ag_generate_noise) + ag_generate_slots store --
+// gen_auction_to with the picks in a per-lane LDS column (P <= kGenSlotsMaxP), the slot count and
+// the filled slots' uniforms from stream 256; Oracle + Truthful populations at any D <= 8
+// (DOS = 0: no LR-TS noise), general ones at the shipped width (DOS = kShipDo).
 template <int P, int D, bool PRUNE, int GENERAL, int BT = kThreads, int DOS = 0, bool GEN = false, int SLOTS = 0>
 __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_MIN_WAVES : AG_TB_MIN_WAVES)
-                                 : (GENERAL ? ((DOS && P > 0 && P <= 2) ? AG_GEN_DOS_MIN_WAVES : AG_GEN_MIN_WAVES)
+                                 : (GENERAL ? ((DOS && P > 0 && P <= 2) ? AG_GEN_DOS_MIN_WAVES
+                                               : (GEN && SLOTS > 0) ? AG_SLOTS_GEN_MIN_WAVES : AG_GEN_MIN_WAVES)
                                             : 1)) void k_simulate(SimParams prm) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int N = prm.N, K = prm.K;
@@ -1087,8 +1112,13 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
   // AG_TS_DMA: every wave's Thompson-noise ring (kTsDmaBufs items of 5 rows x 64 floats)
   constexpr bool kDma = AG_TS_DMA && GENERAL && DOS == 5 && !GEN && BT == kThreads && P >= 1 && P <= AG_TS_DMA_MAXP;
   __shared__ __attribute__((aligned(16))) float s_ring[kDma ? (BT / 64) * kTsDmaBufs * 5 * 64 : 1];
-  static_assert(!GEN || (DOS > 0 && P > 0 && GENERAL), "generate mode: shipped-shape general builds");
-  static_assert(SLOTS == 0 || (P == 0 && !GEN && DOS == 0 && BT == kThreads), "multi-slot: the runtime-P form");
+  static_assert(!GEN || SLOTS > 0 || (DOS > 0 && P > 0 && GENERAL), "generate mode: shipped-shape general builds");
+  static_assert(SLOTS == 0 || (P == 0 && BT == kThreads && (DOS > 0) == (GEN && GENERAL != kGenOracle)),
+                "multi-slot: the runtime-P form; its generate mode draws LR-TS noise at a compile-time width");
+  // multi-slot generate mode: the lane's Floyd picks, one LDS column per lane ([slot][lane]: the
+  // slot loops index them at run time, which a register array could not without scratch)
+  constexpr bool kGenSlots = GEN && SLOTS > 0;
+  __shared__ uint16_t s_picks[kGenSlots ? kGenSlotsMaxP * BT : 1];
   unsigned long long *s_cnt = reinterpret_cast<unsigned long long *>(smem + L.cnt);
 
   const int tid = threadIdx.x;
@@ -1350,16 +1380,45 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
       double x[kMaxD];
       float xf[kMaxD];
       float xabs;
-      load_context(i, x, xf, xabs);
-      int n = ldg(sl.num_slots + i);
-      n = n < 1 ? 1 : (n > sl.max_slots ? sl.max_slots : n);
+      // generate mode: the context, participants (into the lane's LDS column), the slot count
+      // and the filled slots' uniforms drawn here -- the bits ag_generate and ag_generate_slots
+      // store; u0 is the auction's u, sw the stream-256 block last drawn
+      const PickColumn<BT> picks{s_picks + tid};
+      double u0 = 0.0;
+      uint32_t sw[4] = {0u, 0u, 0u, 0u};
+      int n;
+      if constexpr (GEN) {
+        double xe[kMaxD];
+        gen_auction_to<kMaxD>(gk0, gk1, prm.first + i, N, Pn, D - 1, prm.scale, xe, picks, u0);
+        xabs = 1.0f;
+#pragma unroll
+        for (int e = 0; e < D - 1; ++e) {
+          x[e] = xe[e];
+          xf[e] = (float)x[e];
+          xabs += fabsf(xf[e]);
+        }
+        x[D - 1] = 1.0;  // intercept (src/Auction.py:33)
+        xf[D - 1] = 1.0f;
+        xabs *= 1.001f;
+        n = 1;
+        if (sl.max_slots > 1) {  // block 0: the count, and slot 1's uniform
+          gen_slots_block(gk.c0, gk.c1, 0, gk0, gk1, sw);
+          n = gen_num_slots(sw, sl.max_slots);
+        }
+      } else {
+        load_context(i, x, xf, xabs);
+        n = ldg(sl.num_slots + i);
+        n = n < 1 ? 1 : (n > sl.max_slots ? sl.max_slots : n);
+      }
+      auto participant = [&](int s) { return GEN ? (int)picks[s] : (int)ldg(in.part + ((uint32_t)s * B + i)); };
       const int F = n < Pn - 1 ? n : Pn - 1;  // filled slots: zip stops at the second prices
       TopList<SM, true> top;
       top.init();
       for (int s = 0; s < Pn; ++s) {
         const uint32_t o = (uint32_t)s * B + i;
-        const int a = ldg(in.part + o);
-        const SlotResult q = resolve_slot<D, PRUNE, GENERAL>(T, K, x, xf, xabs, a, s, in, B, i, prm.ts_sample != 0);
+        const int a = participant(s);
+        const SlotResult q = resolve_slot<D, PRUNE, GENERAL, false, GEN, DOS>(T, K, x, xf, xabs, a, s, in, B, i,
+                                                                              prm.ts_sample != 0, kTsjLoad, gk);
         store_participant(o, q);
         top.insert(s, q.bid, q.ctr);
       }
@@ -1370,7 +1429,14 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
       for (int k = 0; k < SM; ++k) {
         const bool filled = k < F;
         pk[k] = prm.mech == AG_FIRST_PRICE ? top.bid[k] : top.bid[k + 1];
-        ock[k] = filled ? bernoulli(top.ctr[k], ldg(sl.u + (size_t)k * B + i)) : 0;
+        double uk = 0.0;
+        if constexpr (GEN) {  // a stream-256 block only when a filled slot needs it
+          if (k >= 2 && (k & 1) == 0 && filled) gen_slots_block(gk.c0, gk.c1, (uint32_t)(k >> 1), gk0, gk1, sw);
+          uk = k == 0 ? u0 : gen_u_slot(sw, k);
+        } else if (filled) {
+          uk = ldg(sl.u + (size_t)k * B + i);
+        }
+        ock[k] = filled ? bernoulli(top.ctr[k], uk) : 0;
         if (k == F - 1) lp = pk[k];
         if (k < sl.max_slots) {
           const size_t o = (size_t)k * B + i;
@@ -1394,9 +1460,9 @@ __global__ __launch_bounds__(BT, GENERAL == kGenTruthful ? (P >= 3 ? AG_TB_WIDE_
       if (prm.want_counters) {
         const double lpc = F > 0 ? lp : 0.0;  // nobody charged: the logged price stays 0
         for (int s = 0; s < Pn; ++s) {
-          const int a = ldg(in.part + (uint32_t)s * B + i);
-          const SlotResult q =
-              resolve_slot<D, PRUNE, GENERAL>(T, K, x, xf, xabs, a, s, in, B, i, prm.ts_sample != 0);
+          const int a = participant(s);
+          const SlotResult q = resolve_slot<D, PRUNE, GENERAL, false, GEN, DOS>(T, K, x, xf, xabs, a, s, in, B, i,
+                                                                                prm.ts_sample != 0, kTsjLoad, gk);
           const int r = rank_of(s);
           double price = 0.0, second = 0.0;
           int oc = 0;
@@ -1818,13 +1884,15 @@ typedef void (*SimKernel)(SimParams);
 // The multi-slot builds, one translation unit per SM in {2, 4, 8} (ag_sim_slots.hip):
 // k_simulate<0, D, prune, general, 256 lanes, SLOTS = SM> for D = 2..8, general in {kGenOracle,
 // kGenAll} (nullptr otherwise), and the launch of k_allocate_slots<SM> (stream-ordered).
+// gen: their generate-mode builds -- kGenOracle for D = 2..8, kGenAll for D = 6 at the shipped
+// LR-TS width only (nullptr otherwise).
 template <int SM>
-SimKernel pick_slots_for(int D, bool prune, int general);
+SimKernel pick_slots_for(int D, bool prune, int general, bool gen);
 template <int SM>
 hipError_t launch_allocate_slots_for(const double *bids, const int32_t *num_slots, int max_slots, int64_t B, int P,
                                      int mech, int32_t *winner, double *price, double *second, hipStream_t st);
 #define AG_SLOTS_BUILD(SM)                                                                                       \
-  template <> SimKernel pick_slots_for<SM>(int, bool, int);                                                      \
+  template <> SimKernel pick_slots_for<SM>(int, bool, int, bool);                                                \
   template <> hipError_t launch_allocate_slots_for<SM>(const double *, const int32_t *, int, int64_t, int, int, \
                                                        int32_t *, double *, double *, hipStream_t);
 AG_SLOTS_BUILD(2)

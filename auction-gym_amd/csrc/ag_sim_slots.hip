@@ -3,7 +3,8 @@
 // (ag_sim.h TopList); SM is 2, 4 or 8 and the host picks the smallest that holds the context's
 // max_slots; the Makefile compiles this file once per SM (-DAG_SM), in parallel. 256-lane
 // workgroups, D = E + 1 = 2..8, screened and exact item search, OracleAllocator + TruthfulBidder
-// populations (kGenOracle) and any population (kGenAll).
+// populations (kGenOracle) and any population (kGenAll); and their generate-mode builds
+// (ag_simulate_slots_generated), which draw every input in the kernel.
 #include "ag_sim.h"
 
 #ifndef AG_SM
@@ -27,8 +28,27 @@ SimKernel pick_d(int D) {
   }
 }
 
+// the generate-mode builds (ag_simulate_slots_generated): Oracle + Truthful populations at every
+// D; general populations at the shipped width only (the generate mode's LR-TS noise is drawn at a
+// compile-time width, ts_gen_item)
+template <int SM, bool PRUNE>
+SimKernel pick_gen_d(int D, int general) {
+  if (general) return D == 6 ? k_simulate<0, 6, PRUNE, kGenAll, kThreads, kShipDo, true, SM> : nullptr;
+  switch (D) {
+    case 2: return k_simulate<0, 2, PRUNE, kGenOracle, kThreads, 0, true, SM>;
+    case 3: return k_simulate<0, 3, PRUNE, kGenOracle, kThreads, 0, true, SM>;
+    case 4: return k_simulate<0, 4, PRUNE, kGenOracle, kThreads, 0, true, SM>;
+    case 5: return k_simulate<0, 5, PRUNE, kGenOracle, kThreads, 0, true, SM>;
+    case 6: return k_simulate<0, 6, PRUNE, kGenOracle, kThreads, 0, true, SM>;
+    case 7: return k_simulate<0, 7, PRUNE, kGenOracle, kThreads, 0, true, SM>;
+    case 8: return k_simulate<0, 8, PRUNE, kGenOracle, kThreads, 0, true, SM>;
+    default: return nullptr;
+  }
+}
+
 template <int SM>
-SimKernel pick_sm(int D, bool prune, int general) {
+SimKernel pick_sm(int D, bool prune, int general, bool gen) {
+  if (gen) return prune ? pick_gen_d<SM, true>(D, general) : pick_gen_d<SM, false>(D, general);
   if (general) return prune ? pick_d<SM, true, kGenAll>(D) : pick_d<SM, false, kGenAll>(D);
   return prune ? pick_d<SM, true, kGenOracle>(D) : pick_d<SM, false, kGenOracle>(D);
 }
@@ -66,8 +86,8 @@ __global__ __launch_bounds__(kThreads) void k_allocate_slots(const double *__res
 }  // namespace
 
 template <>
-SimKernel pick_slots_for<AG_SM>(int D, bool prune, int general) {
-  return pick_sm<AG_SM>(D, prune, general);
+SimKernel pick_slots_for<AG_SM>(int D, bool prune, int general, bool gen) {
+  return pick_sm<AG_SM>(D, prune, general, gen);
 }
 
 template <>

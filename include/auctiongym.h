@@ -313,7 +313,7 @@ int ag_allocate(ag_ctx *ctx, const double *bids, int64_t B, int32_t *winner, dou
  * start of an iteration, like Agent.clear_utility); may be NULL.
  * One slot per auction: on a context with num_slots > 1 this, ag_simulate_generated,
  * ag_lrts_collect and ag_shading_collect return AG_ERR_UNSUPPORTED (use ag_simulate_slots,
- * ag_lrts_collect_slots and ag_shading_collect_slots). */
+ * ag_simulate_slots_generated, ag_lrts_collect_slots and ag_shading_collect_slots). */
 int ag_simulate(ag_ctx *ctx, int64_t B, const ag_batch_in *in, ag_batch_out *out,
                 int64_t *counters_fx, void *stream);
 
@@ -421,6 +421,36 @@ int ag_allocate_slots(ag_ctx *ctx, const double *bids, const int32_t *num_slots,
  * otherwise AG_ERR_UNSUPPORTED. (Round 6: the general populations; ABI unchanged.) */
 int ag_simulate_generated(ag_ctx *ctx, uint64_t seed, uint64_t first_auction, int64_t B, ag_batch_out *out,
                           int64_t *counters_fx, void *stream);
+
+/* Generate mode for multi-slot rounds: B rounds of ag_simulate_slots whose inputs are all drawn
+ * inside the SLOTS builds of the simulate kernel, the same bits ag_generate(seed, first_auction, B)
+ * (+ ag_generate_noise) and ag_generate_slots(seed, first_auction, B) write -- so every ag_slots_out
+ * field and every counter limb equals those calls followed by ag_simulate_slots, bit for bit; nothing
+ * but the catalogue and the agents' parameters is read from HBM. A stream-256 block is drawn only
+ * when a filled slot k < F = min(num_slots, P - 1) needs it. max_slots = ag_shape.num_slots, 1
+ * included (there winner[0], price[0], second_price[0], outcome[0] and the counters are
+ * ag_simulate_generated's). P <= 16 (the participants' Floyd picks live in a per-lane column of
+ * LDS; the three-call path serves P <= 64), E + 1 <= 8. OracleAllocator + TruthfulBidder
+ * populations at every such shape; general populations in the shipped shape (E = 5, OE = 4) except
+ * ValueLearningBidders bidding by search (their grids are not drawn); otherwise
+ * AG_ERR_UNSUPPORTED with the reason in ag_last_error. B * max(P, max_slots) < 2^31. Hot call.
+ * (New function; ABI unchanged.) */
+int ag_simulate_slots_generated(ag_ctx *ctx, uint64_t seed, uint64_t first_auction, int64_t B, ag_slots_out *out,
+                                int64_t *counters_fx, void *stream);
+
+/* Synthetic slot counts and click uniforms of multi-slot rounds, auctions [first_auction,
+ * first_auction + B) (dev; either output may be NULL): with S = ag_shape.num_slots (max_slots),
+ * num_slots [B] = 1 + ((w0 * S) >> 32) in 1..S, w0 word 0 of block 0 of stream 256 (the participant
+ * picks' multiply-shift; rng.integers(1, max_slots + 1) of src/Auction.py:30 in distribution; word 1
+ * is unused); u_slots [S][B], all S rows written: row 0 is ag_generate's u (stream 0, block 0, words
+ * 0-1), row k = 1..7 the 53-bit uniform of words 2 (k & 1), 2 (k & 1) + 1 of block k / 2 of stream
+ * 256 (k = 1: words 2-3 of block 0). Same Philox key / counter scheme as ag_generate; no draw of an
+ * auction shares a (block, stream) with another (csrc/ag_philox.h; tests/gen_slots_reference.py
+ * states it in numpy). With ag_generate, ag_generate_noise and ag_generate_search_grid this gives
+ * every input ag_simulate_slots takes. Works on any context, num_slots = 1 included (every count 1,
+ * row 0 = u). Hot call: stream-ordered, no allocation, no synchronisation. */
+int ag_generate_slots(ag_ctx *ctx, uint64_t seed, uint64_t first_auction, int64_t B, int32_t *num_slots,
+                      double *u_slots, void *stream);
 
 /* Synthetic replay inputs for auctions [first_auction, first_auction + B) (dev, SoA):
  * Philox4x32-10 keyed by seed and the GLOBAL auction index, so a sharded batch is
