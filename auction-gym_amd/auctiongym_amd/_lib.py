@@ -49,7 +49,7 @@ EXPORTS = ("ag_create", "ag_destroy", "ag_set_agent_kinds", "ag_set_agent_params
            "ag_abi_version", "ag_ts_noise_index", "ag_generate_ts_noise_compact", "ag_torch_normal_epochs",
            "ag_bidder_rp_begin", "ag_bidder_rp_epoch", "ag_bidder_rp_run", "ag_bidder_rp_noise", "ag_bidder_rp_poll", "ag_bidder_rp_end",
            "ag_lrts_rp_begin", "ag_lrts_rp_epoch", "ag_lrts_rp_poll", "ag_lrts_rp_end", "ag_empirical_update_agents",
-           "ag_coop_selftest", "ag_div_selftest",
+           "ag_coop_selftest", "ag_div_selftest", "ag_math_kat",
            "ag_simulate_slots", "ag_allocate_slots", "ag_replay_draw_slots", "ag_replay_draw_population_slots",
            "ag_lrts_collect_slots", "ag_shading_collect_slots", "ag_generate_slots", "ag_simulate_slots_generated")
 ABI_VERSION = 17
@@ -59,6 +59,23 @@ VL_SEARCH, VL_POLICY = 0, 1
 PL_LOSSES = {"REINFORCE": 0, "REINFORCE_offpolicy": 1, "TRPO": 2, "PPO": 3}
 LRTS_MAX_EPOCHS = 16384
 LRTS_MAX_DO = 8
+# ag_math_kat's function table (AG_KAT_*): name -> (fn, input dtype, output dtype), one record
+# per element; a structured dtype where a record has several fields
+KAT = {name: (fn, i, o) for fn, (name, i, o) in enumerate((
+    ("exp", "<f8", "<u8"), ("exp_fast", "<f8", "<u8"), ("sigmoid", "<f8", "<u8"), ("sigmoid_fast", "<f8", "<u8"),
+    ("exp_main", "<f8", [("v", "<u8"), ("ok", "<u8")]),
+    ("expf_glibc", "<f4", "<u4"), ("torch_expf", "<f4", "<u4"),
+    ("ts_ctr_of", [("z", "<f4"), ("k", "<i4"), ("K", "<i4")], "<u4"),
+    ("log1p", "<f8", "<u8"), ("log1p_main", "<f8", [("v", "<u8"), ("ok", "<u8")]),
+    ("log1p_shared", "<f8", [("v", "<u8"), ("flags", "<u8")]),
+    ("div", [("a", "<f8"), ("b", "<f8")], [("v", "<u8"), ("safe", "<u8")]),
+    ("fxb", "<f8", "<i8"), ("fxb_fast", "<f8", "<i8"), ("fxb_x", "<f8", "<i8"),
+    ("fx_round_grad", "<f8", "<i8"), ("fx_round_loss", "<f8", "<i8"),
+    ("polar", [("u", "<f8"), ("s", "<f8")], "<u8"),
+    ("lr_bce", [("p", "<f4"), ("y", "<i4")], "<i8"),
+    ("softplus_fast", "<f8", [("v", "<u8"), ("e", "<u8")]),
+    ("wr_row", "<f8", [("p", "<u8"), ("Lz", "<u8")]),
+))}
 
 
 class AgShape(ctypes.Structure):
@@ -179,6 +196,7 @@ def load(path=None):
         "ag_stream_copy": (ctypes.c_int, [vp, vp, i64, vp]),
         "ag_coop_selftest": (ctypes.c_int, [i32, i32, i32, i32, ctypes.POINTER(i64)]),
         "ag_div_selftest": (ctypes.c_int, [i32, i64, u64, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
+        "ag_math_kat": (ctypes.c_int, [i32, i32, vp, i64, vp]),
         "ag_estimate_ctr": (ctypes.c_int, [vp, i32, i64, vp, vp, vp, vp]),
         "ag_bid": (ctypes.c_int, [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "ag_replay_draw": (ctypes.c_int, [ctypes.POINTER(AgPcg64State), i64, i32, i32, i32, ctypes.c_double, i32,
@@ -222,6 +240,18 @@ def load(path=None):
         f.argtypes = args
     _libs[path] = L
     return L
+
+
+def math_kat(name, x, device=0, lib=None):
+    """ag_math_kat: function `name` of KAT over the numpy records x (converted to the function's
+    input dtype) on `device` (-1: the host build of the same source); the result bits."""
+    import numpy as np
+    fn, it, ot = KAT[name]
+    x = np.ascontiguousarray(x, dtype=np.dtype(it))
+    out = np.empty(x.shape[0], dtype=np.dtype(ot))
+    L = lib or load()
+    check(L.ag_math_kat(device, fn, x.ctypes.data, x.shape[0], out.ctypes.data), "ag_math_kat", L)
+    return out
 
 
 def check(rc, what="", lib=None):

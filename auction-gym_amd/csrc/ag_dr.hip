@@ -42,8 +42,11 @@
 #include "ag_philox.h"
 #include "ag_coop.h"
 #include "ag_div.h"
+#include "ag_train_math.h"
 
 namespace {
+
+using namespace agtm;
 
 using agcoop::agent_barrier;
 using agcoop::bar_lines;
@@ -66,30 +69,9 @@ constexpr size_t kRecLdsBytes0 = AG_DR_REC_LDS0;  // record cache per workgroup,
 #define AG_DR_PH1_MIN_WAVES 3  // the later fits: <= 168 VGPRs, 3 waves per SIMD (FP_DR_TS update 1.96 -> 1.69 s)
 #endif
 constexpr size_t kRecLdsBytes = AG_DR_REC_LDS;  // record cache per workgroup, later fits
-constexpr double kGrid = 0x1p40, kInv = 0x1p-40;
 constexpr int64_t kLo24 = (int64_t(1) << 24) - 1;
 
-// Fixed-point terms (int64)rint(v * 2^40). For |v * 2^40| < 2^51 (every term in practice)
-// adding 1.5 * 2^52 rounds to the integer (nearest, ties to even, as rint) and leaves it in
-// the low mantissa bits.
-// The accumulators hold them biased: fxb(v) = (int64)rint(v * 2^40) + kFxMagic (mod 2^64),
-// kFxMagic = the bits of 1.5 * 2^52 -- for |v * 2^40| < 2^51 simply the bits of v * 2^40 +
-// 1.5 * 2^52, so a term costs one add and the 64-bit accumulate (no subtract); a lane that
-// added n terms to an accumulator takes n * kFxMagic off once (fx_unbias) before the exact
-// sums. Integer arithmetic mod 2^64: the same totals, bit for bit.
-constexpr uint64_t kFxMagic = 0x4338000000000000ull;  // asu64(0x1.8p52)
-__device__ __forceinline__ int64_t fxb_fast(double v) {  // |v| <= 2^10 guaranteed by the caller
-  return (int64_t)agexp::asu64(v * kGrid + 0x1.8p52);
-}
-__device__ __forceinline__ int64_t fxb(double v) {
-  const double x = v * kGrid;
-  if (__builtin_expect(__builtin_fabs(x) < 0x1p51, 1)) return (int64_t)agexp::asu64(x + 0x1.8p52);
-  return (int64_t)((uint64_t)(int64_t)__builtin_rint(x) + kFxMagic);
-}
-// fxb's fast path on x = v * 2^40 already formed, and its range test (callers test a
-// record's terms together and take fxb for all of them when one is out of range)
-__device__ __forceinline__ int64_t fxb_x(double x) { return (int64_t)agexp::asu64(x + 0x1.8p52); }
-__device__ __forceinline__ bool fx_in(double x) { return __builtin_fabs(x) < 0x1p51; }
+// the fixed-point terms and their biased forms (fxb, fxb_fast, fxb_x, fx_in): ag_train_math.h
 __device__ __forceinline__ void addw(int64_t &a, int64_t t) { a = (int64_t)((uint64_t)a + (uint64_t)t); }
 __device__ __forceinline__ void fx_unbias(int64_t &a, int64_t n) {
   a = (int64_t)((uint64_t)a - (uint64_t)n * kFxMagic);
@@ -104,27 +86,8 @@ __device__ __forceinline__ double fxv(int64_t hi, int64_t lo) {
 // softplus(u) = u > 20 ? u : log1p(exp(u)) and its derivative exp(u) / (exp(u) + 1), from
 // e = exp(u) (the forward pass keeps it for the backward pass)
 __device__ __forceinline__ double dsoftplus_e(double u, double e) { return u > 20.0 ? 1.0 : e / (e + 1.0); }
-// log1p_main's divisions for a caller that holds r = the reciprocal of its 1 + x (ag_div.h)
-struct SharedDiv {
-  double r;
-  __device__ double cu(double c, double u) const { return agdiv::div_core(c, u, r); }
-  __device__ double fs(double f, double d) const { return agdiv::div_core(f, d, agdiv::recip(d)); }
-};
-
-// exp(x) and softplus from the branch-free main paths (the same bits), the rare inputs
-// outside them patched with the full functions
+// SharedDiv (log1p_main's divisions from a shared reciprocal) and softplus_fast: ag_train_math.h
 using agexp::exp_fast;
-// e = exp(u); returns softplus(u)
-__device__ __forceinline__ double softplus_fast(double u, double &e, const uint64_t *tab) {
-  e = agexp::exp_main(u, tab);
-  bool lok;
-  double l = aglog1p::log1p_main(e, lok);
-  if (__builtin_expect(!(agexp::exp_in_main(u) && (lok || u > 20.0)), 0)) {
-    e = agexp::exp(u, tab);
-    l = aglog1p::log1p(e);
-  }
-  return u > 20.0 ? u : l;
-}
 
 // Exact block sum of NV per-lane int64 accumulators (each split at bit 24 so nothing can
 // overflow): every thread gets the totals as (hi, lo) pairs in s_out.
@@ -502,7 +465,7 @@ __device__ __forceinline__ double fit_eps(const FitNoise &F, int e, int64_t i) {
     }
   }
   if (!found) return 0.0;
-  return (double)(float)(u * __builtin_sqrt(-2.0 * aglog1p::log1p(s - 1.0) / s));
+  return polar_transform(u, s);
 }
 
 // records of the workgroup: [c0, c0 + nb) of the agent's n
@@ -573,45 +536,8 @@ __device__ __forceinline__ void each_record(const RecView &V, int64_t nb, F &&f)
   for (; j < nb; j += kDrThreads) f(j, std::false_type());
 }
 
-// One BCE row of the win-rate fit (its loss and gradient terms, biased: see fxb) at the model
-// (w0, w1, w2, w3). One exp per row (oracle/ag_oracle_dr.c fit_winrate): e = exp(-|z|), L =
-// log1p(e); p = (z >= 0 ? 1 : e) / (1 + e); -log(p) = softplus(-z) for a win, -log(1 - p) =
-// softplus(z) otherwise, softplus(u) = L for u <= 0, |z| + L for u > 0 (u past 20: u).
-// Branch-free main paths of exp and log1p (the same bits), the rare inputs outside them
-// patched with the full functions afterwards. aug: the gamma = 0, y = 0 augmentation row.
-// The row in two parts so that a record's two rows (and a lane's records) can be computed
-// in one basic block before either takes its rare branch: wr_main is branch-free, wr_finish
+// One BCE row of the win-rate fit: wr_main (branch-free) and wr_patch (ag_train_math.h); wr_finish
 // patches (rarely) and adds the terms.
-struct WrMain {
-  double z, a, e, Lz, pw, u, t, gz, x2, x3;
-  bool main;  // exp and log1p on their main paths
-  bool ok;    // main, and the checked terms in fxb's fast range
-};
-__device__ __forceinline__ WrMain wr_main(double c, double v, double g, double y, bool aug, double w0, double w1,
-                                          double w2, double w3, const uint64_t *tab) {
-  WrMain m;
-  m.z = c * w0 + v * w1 + g * w2 + w3;
-  m.a = __builtin_fabs(m.z);
-  m.e = agexp::exp_main(-m.a, tab);
-  bool lok;
-  // p's division and log1p's c / u both divide by 1 + e: one reciprocal (ag_div.h; on the main
-  // paths e >= exp(-512), c is 0 or >= 2^-81 in magnitude, |f| >= 2^-53: div_safe's range)
-  const double d1 = 1.0 + m.e, r1 = agdiv::recip(d1);
-  m.Lz = aglog1p::log1p_main_t(m.e, lok, SharedDiv{r1});
-  m.pw = agdiv::div_core(m.z >= 0.0 ? 1.0 : m.e, d1, r1);
-  m.u = y > 0.0 ? -m.z : m.z;
-  m.t = fmin(m.u > 20.0 ? m.u : (m.u > 0.0 ? m.a + m.Lz : m.Lz), 100.0);
-  m.gz = m.pw - y;
-  // |t| <= 100, |pw - y| <= 1, ctr in [0, 1]: those terms are far inside fxb's fast range;
-  // gz * value and gz * gamma are checked. ONE rare branch per row (the exp / log1p patch and
-  // an out-of-range term together) instead of one per patch: the common path stays straight.
-  // (the augmentation row's x3 is gz * 0: always in range, and its term is never added)
-  m.x2 = (m.gz * v) * kGrid;
-  m.x3 = (m.gz * g) * kGrid;
-  m.main = (int)agexp::exp_in_main(m.a) & (int)lok;
-  m.ok = (int)m.main & (int)fx_in(m.x2) & ((int)aug | (int)fx_in(m.x3));
-  return m;
-}
 __device__ __forceinline__ void wr_finish(int64_t (&acc)[5], WrMain m, double c, double v, double g, double y,
                                           bool aug, const uint64_t *tab) {
   int64_t t2, t3;
@@ -619,13 +545,7 @@ __device__ __forceinline__ void wr_finish(int64_t (&acc)[5], WrMain m, double c,
     t2 = fxb_x(m.x2);
     t3 = fxb_x(m.x3);
   } else {
-    if (!m.main) {
-      m.e = agexp::exp(-m.a, tab);
-      m.Lz = aglog1p::log1p(m.e);
-      m.pw = (m.z >= 0.0 ? 1.0 : m.e) / (1.0 + m.e);
-      m.t = fmin(m.u > 20.0 ? m.u : (m.u > 0.0 ? m.a + m.Lz : m.Lz), 100.0);
-      m.gz = m.pw - y;
-    }
+    if (!m.main) wr_patch(m, y, tab);
     t2 = fxb(m.gz * v);
     t3 = fxb(m.gz * g);
   }

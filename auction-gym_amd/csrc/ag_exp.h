@@ -9,7 +9,10 @@
 // Algorithm (glibc's table-driven exp; restated, not copied): x = k*ln2/128 + r,
 // exp(x) = 2^(k/128) * exp(r), 2^(k/128) from a 128-entry table (ag_exp_table.h, built by
 // tools/gen_exp_table.py), exp(r) - 1 by a degree-5 polynomial, with the FMAs placed
-// where the FMA build of glibc contracts them. The host test
+// where the FMA build of glibc contracts them -- the table index k included: kd = fma(InvLn2N,
+// x, Shift), which differs from the rounded product plus Shift exactly where x InvLn2N is within
+// a rounding of half-way between two integers (tests/math_kat_cases.py puts inputs there; a
+// random sweep never does). The host test
 // (tests/test_exp_restatement.py) compares this exact source, compiled for the CPU,
 // against the host libm on 4e7 inputs over the full double range; the GPU test compares
 // the device build against the same libm.
@@ -81,8 +84,7 @@ AG_HD double exp(double x, const uint64_t *tab) {
     }
     abstop = 0;  // large |x|: exp_special below
   }
-  double z = kInvLn2N * x;
-  double kd = z + kShift;
+  double kd = fma(kInvLn2N, x, kShift);  // one rounding: the FMA build contracts z = InvLn2N x into the shift
   uint64_t ki = asu64(kd);
   kd -= kShift;
   double r = fma(kd, kNegLn2LoN, fma(kd, kNegLn2HiN, x));
@@ -105,8 +107,7 @@ AG_HD bool exp_in_main(double x) {
   return abstop - 0x3c9u < 0x408u - 0x3c9u;
 }
 AG_HD double exp_main(double x, const uint64_t *tab) {
-  double z = kInvLn2N * x;
-  double kd = z + kShift;
+  double kd = fma(kInvLn2N, x, kShift);  // one rounding: the FMA build contracts z = InvLn2N x into the shift
   uint64_t ki = asu64(kd);
   kd -= kShift;
   double r = fma(kd, kNegLn2LoN, fma(kd, kNegLn2HiN, x));

@@ -25,8 +25,11 @@
 #include "ag_exp_table.h"
 #include "ag_host.h"
 #include "ag_coop.h"
+#include "ag_train_math.h"
 
 namespace {
+
+using namespace agtm;
 
 constexpr int kLrThreads = 256;        // 4 waves; one sample per lane per pass
 constexpr int kLrEpochs = AG_LRTS_MAX_EPOCHS;
@@ -36,12 +39,9 @@ constexpr int kLrCache = 16;           // samples per lane kept in registers (1 
 constexpr int kAccStride = kLrThreads + 1;  // [column][lane] int64 tile, padded: the column
                                             // reduction (lanes = columns) is conflict-free
 constexpr int kHistory = 100;          // losses[-100] of the early stop
-constexpr double kGradScale = 0x1p40, kLossScale = 0x1p32;
 constexpr int64_t kLo24 = (int64_t(1) << 24) - 1;
 
-__device__ __forceinline__ int64_t fx_round(double v, double scale) {
-  return (int64_t)__builtin_rint(v * scale);
-}
+// fx_round, kGradScale / kLossScale and the BCE term lr_bce_term: ag_train_math.h
 // (hi, lo) partial sums of values split at bit 24 -> the exact sum S read back as
 // (double)(S >> 24) * 2^24 + (double)(S & (2^24 - 1)) (ora_lrts_update's fx_read).
 __device__ __forceinline__ double fx_read(int64_t hi, int64_t lo, double inv_scale) {
@@ -150,7 +150,7 @@ __device__ __forceinline__ int64_t lr_epoch_sample(const LrSample &s, const floa
                                                    int64_t *__restrict__ acc, const uint64_t *tab) {
   const float z = lr_logit<DO>(sm + s.item * DO, s.x);
   const float p = 1.0f / (1.0f + (float)agexp::exp_fast(-(double)z, tab));
-  const double t = s.y ? -fmax(log((double)p), -100.0) : -fmax(log1p(-(double)p), -100.0);
+  const double t = lr_bce_term(p, s.y);
   const double gz = (double)p - (double)s.y;
 #pragma unroll
   for (int d = 0; d < DO; ++d) acc[(s.item * DO + d) * kAccStride] += fx_round(gz * (double)s.x[d], kGradScale);

@@ -7,6 +7,9 @@
 // out of order) shows up as a wrong total or a hang, so tests/test_gpu_coop.py runs it under a
 // time limit on the built form (AG_COOP_FENCED 0 by default; the fenced form is the A/B build
 // `make variant NAME=fenced VFLAGS=-DAG_COOP_FENCED=1`).
+// Also ag_div_selftest (ag_div.h's split division against `a / b`) and ag_math_kat: the small
+// functions every parity claim rests on, evaluated on caller-chosen inputs by the device build
+// or by the host build of the same source.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -14,6 +17,8 @@
 #include "ag_coop.h"
 #include "ag_div.h"
 #include "ag_host.h"
+#include "ag_sim.h"
+#include "ag_train_math.h"
 
 namespace {
 
@@ -126,7 +131,160 @@ __global__ __launch_bounds__(256) void k_div_stress(uint64_t seed, int iters, un
   atomicAdd(tested, n);
 }
 
+// ---------------------------------------------------------------------------------------
+// ag_math_kat: function `fn` of include/auctiongym.h's table on element i. One source for the
+// device kernel and the host loop; every function called is the kernels' own (ag_exp.h,
+// ag_log1p.h, ag_div.h, ag_sim.h, ag_train_math.h). `tab`: the kExpTabLds-entry table.
+// ---------------------------------------------------------------------------------------
+struct KatIo {
+  int in_bytes, out_bytes;
+};
+__host__ __device__ __forceinline__ KatIo kat_io(int fn) {
+  switch (fn) {
+    case AG_KAT_EXP: case AG_KAT_EXP_FAST: case AG_KAT_SIGMOID: case AG_KAT_SIGMOID_FAST: case AG_KAT_LOG1P:
+    case AG_KAT_FXB: case AG_KAT_FXB_FAST: case AG_KAT_FXB_X: case AG_KAT_FX_ROUND_GRAD: case AG_KAT_FX_ROUND_LOSS:
+    case AG_KAT_LR_BCE:
+      return {8, 8};
+    case AG_KAT_EXP_MAIN: case AG_KAT_LOG1P_MAIN: case AG_KAT_LOG1P_SHARED: case AG_KAT_SOFTPLUS_FAST:
+    case AG_KAT_WR_ROW:
+      return {8, 16};
+    case AG_KAT_EXPF_GLIBC: case AG_KAT_TORCH_EXPF:
+      return {4, 4};
+    case AG_KAT_TS_CTR_OF:
+      return {12, 4};
+    case AG_KAT_DIV:
+      return {16, 16};
+    case AG_KAT_POLAR:
+      return {16, 8};
+    default:
+      return {0, 0};
+  }
+}
+// SharedDiv with the operands of its two divisions tested against div_safe on the way
+struct KatSharedDiv {
+  agtm::SharedDiv d;
+  bool *safe_cu, *safe_fs;
+  __host__ __device__ double cu(double c, double u) const {
+    *safe_cu = agdiv::div_safe(c, u);
+    return d.cu(c, u);
+  }
+  __host__ __device__ double fs(double f, double dd) const {
+    *safe_fs = agdiv::div_safe(f, dd);
+    return d.fs(f, dd);
+  }
+};
+__host__ __device__ __forceinline__ void kat_eval(int fn, const void *in, void *out, int64_t i, const uint64_t *tab) {
+  using agexp::asu64;
+  const double *xd = (const double *)in;
+  const float *xf = (const float *)in;
+  uint64_t *od = (uint64_t *)out;
+  uint32_t *of = (uint32_t *)out;
+  switch (fn) {
+    case AG_KAT_EXP: od[i] = asu64(agexp::exp(xd[i], tab)); break;
+    case AG_KAT_EXP_FAST: od[i] = asu64(agexp::exp_fast(xd[i], tab)); break;
+    case AG_KAT_SIGMOID: od[i] = asu64(agexp::sigmoid(xd[i], tab)); break;
+    case AG_KAT_SIGMOID_FAST: od[i] = asu64(agexp::sigmoid_fast(xd[i], tab)); break;
+    case AG_KAT_EXP_MAIN:
+      od[2 * i] = asu64(agexp::exp_main(xd[i], tab));
+      od[2 * i + 1] = agexp::exp_in_main(xd[i]);
+      break;
+    case AG_KAT_EXPF_GLIBC: of[i] = __builtin_bit_cast(uint32_t, agexp::expf_glibc(xf[i], tab + 256)); break;
+    case AG_KAT_TORCH_EXPF: of[i] = __builtin_bit_cast(uint32_t, ag::torch_expf(xf[i])); break;
+    case AG_KAT_TS_CTR_OF: {
+      const int32_t *q = (const int32_t *)in + 3 * i;
+      of[i] = __builtin_bit_cast(uint32_t, ag::ts_ctr_of(xf[3 * i], q[1], q[2], tab));
+      break;
+    }
+    case AG_KAT_LOG1P: od[i] = asu64(aglog1p::log1p(xd[i])); break;
+    case AG_KAT_LOG1P_MAIN: {
+      bool ok;
+      od[2 * i] = asu64(aglog1p::log1p_main(xd[i], ok));
+      od[2 * i + 1] = ok;
+      break;
+    }
+    case AG_KAT_LOG1P_SHARED: {
+      bool ok, s1 = false, s2 = false;
+      const double r = agdiv::recip(1.0 + xd[i]);
+      od[2 * i] = asu64(aglog1p::log1p_main_t(xd[i], ok, KatSharedDiv{agtm::SharedDiv{r}, &s1, &s2}));
+      od[2 * i + 1] = (uint64_t)ok | ((uint64_t)s1 << 1) | ((uint64_t)s2 << 2);
+      break;
+    }
+    case AG_KAT_DIV: {
+      const double a = xd[2 * i], b = xd[2 * i + 1];
+      od[2 * i] = asu64(agdiv::div_core(a, b, agdiv::recip(b)));
+      od[2 * i + 1] = agdiv::div_safe(a, b);
+      break;
+    }
+    case AG_KAT_FXB: od[i] = (uint64_t)agtm::fxb(xd[i]); break;
+    case AG_KAT_FXB_FAST: od[i] = (uint64_t)agtm::fxb_fast(xd[i]); break;
+    case AG_KAT_FXB_X: od[i] = (uint64_t)agtm::fxb_x(xd[i]); break;
+    case AG_KAT_FX_ROUND_GRAD: od[i] = (uint64_t)agtm::fx_round(xd[i], agtm::kGradScale); break;
+    case AG_KAT_FX_ROUND_LOSS: od[i] = (uint64_t)agtm::fx_round(xd[i], agtm::kLossScale); break;
+    case AG_KAT_POLAR: od[i] = asu64(agtm::polar_transform(xd[2 * i], xd[2 * i + 1])); break;
+    case AG_KAT_LR_BCE: {
+      const int32_t y = ((const int32_t *)in)[2 * i + 1];
+      od[i] = (uint64_t)agtm::fx_round(agtm::lr_bce_term(xf[2 * i], y), agtm::kLossScale);
+      break;
+    }
+    case AG_KAT_SOFTPLUS_FAST: {
+      double e;
+      od[2 * i] = asu64(agtm::softplus_fast(xd[i], e, tab));
+      od[2 * i + 1] = asu64(e);
+      break;
+    }
+    case AG_KAT_WR_ROW: {  // a y = 0 row whose logit is the input: z = 0 0 + 0 0 + 0 0 + x
+      agtm::WrMain m = agtm::wr_main(0.0, 0.0, 0.0, 0.0, false, 0.0, 0.0, 0.0, xd[i], tab);
+      if (!m.main) agtm::wr_patch(m, 0.0, tab);
+      od[2 * i] = asu64(m.pw);
+      od[2 * i + 1] = asu64(m.Lz);
+      break;
+    }
+    default: break;
+  }
+}
+__global__ __launch_bounds__(256) void k_math_kat(int fn, const void *in, void *out, int64_t n) {
+  __shared__ uint64_t s_tab[agexp::kExpTabLds];
+  for (int i = threadIdx.x; i < 256; i += 256) s_tab[i] = ag_exp_tab[i];
+  if (threadIdx.x < 32) s_tab[256 + threadIdx.x] = agexp::expf_tab_entry(ag_exp_tab, threadIdx.x);
+  __syncthreads();
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    kat_eval(fn, in, out, i, s_tab);
+}
+
 }  // namespace
+
+extern "C" int ag_math_kat(int32_t device, int32_t fn, const void *in, int64_t n, void *out) {
+  const KatIo io = kat_io(fn);
+  if (io.in_bytes == 0) return ag_set_error(AG_ERR_INVALID, "ag_math_kat: fn %d outside [0, %d)", fn, AG_KAT_COUNT);
+  if (n < 0 || device < -1 || ((!in || !out) && n > 0))
+    return ag_set_error(AG_ERR_INVALID, "ag_math_kat: device >= -1, n >= 0, non-null in / out");
+  if (n == 0) return AG_OK;
+  if (device < 0) {  // the host build of the same source
+    uint64_t tab[agexp::kExpTabLds];
+    for (int i = 0; i < 256; ++i) tab[i] = ag_exp_tab[i];
+    for (int j = 0; j < 32; ++j) tab[256 + j] = agexp::expf_tab_entry(ag_exp_tab, j);
+    for (int64_t i = 0; i < n; ++i) kat_eval(fn, in, out, i, tab);
+    return AG_OK;
+  }
+  AgDeviceGuard dg(device);
+  void *d_in = nullptr, *d_out = nullptr;
+  const size_t nin = (size_t)n * io.in_bytes, nout = (size_t)n * io.out_bytes;
+  hipError_t e = hipMalloc(&d_in, nin);
+  if (e == hipSuccess) e = hipMalloc(&d_out, nout);
+  if (e == hipSuccess) e = hipMemcpy(d_in, in, nin, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    const int64_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(k_math_kat, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, nullptr, fn,
+                       (const void *)d_in, d_out, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, d_out, nout, hipMemcpyDeviceToHost);
+  (void)hipFree(d_in);
+  (void)hipFree(d_out);
+  if (e != hipSuccess) return ag_set_error(AG_ERR_HIP, "ag_math_kat: %s", hipGetErrorString(e));
+  return AG_OK;
+}
 
 extern "C" int ag_div_selftest(int32_t device, int64_t pairs, uint64_t seed, int64_t *tested, int64_t *mismatches) {
   if (!mismatches || !tested || pairs < 0)

@@ -559,7 +559,7 @@ __device__ __forceinline__ void ts_dma_item5(const float *src, uint32_t lds_any)
 // torch's float32 exp on the CPU as torch.sigmoid's vectorised path computes it (SLEEF's
 // expf_u10; oracle/ag_oracle_dr.c torch_expf bit for bit): q = round(x / ln 2), the reduced
 // argument in two fused steps, a degree-5 fused Horner polynomial, times 2^q in two steps.
-__device__ __forceinline__ float torch_expf(float d) {
+__host__ __device__ __forceinline__ float torch_expf(float d) {
   const float q = __builtin_rintf(d * 1.442695040888963407359924681001892137426645954152985934135449406931f);
   float s = __builtin_fmaf(q, -0.693145751953125f, d);
   s = __builtin_fmaf(q, -1.428606765330187045e-06f, s);
@@ -595,7 +595,7 @@ __device__ __forceinline__ float ts_logit_w(const float *wd, const float *x, int
   for (int d = 1; d < Do; ++d) z = z + wd[d] * x[d];
   return z;
 }
-__device__ __forceinline__ float ts_ctr_of(float z, int k, int K, const uint64_t *tab) {
+__host__ __device__ __forceinline__ float ts_ctr_of(float z, int k, int K, const uint64_t *tab) {
   const float e = k < (K & ~31) ? torch_expf(-z) : agexp::expf_glibc(-z, tab + 256);
   return 1.0f / (1.0f + e);
 }

@@ -845,6 +845,41 @@ int ag_coop_selftest(int32_t device, int32_t workgroups, int32_t generations, in
  * reference counterpart. */
 int ag_div_selftest(int32_t device, int64_t pairs, uint64_t seed, int64_t *tested, int64_t *mismatches);
 
+/* Known answers of the small functions every parity claim rests on (csrc/ag_exp.h, ag_log1p.h,
+ * ag_div.h, ag_train_math.h, the simulate kernels' torch_expf / ts_ctr_of): function `fn` applied
+ * to `n` inputs, the result BITS returned. in / out are host arrays of n records, laid out as
+ * listed per function (f64 / u64 / i64 words of 8 bytes, f32 / u32 / i32 of 4). device >= 0: a
+ * plain kernel on that device, one element per thread, the exp table in LDS as in the product
+ * kernels; device = -1: the host build of the same source (where the hardware reciprocal does
+ * not exist, agdiv::div_core is the plain a / b). fn outside the table, n < 0, device < -1 or a
+ * null pointer with n > 0: AG_ERR_INVALID. Synchronous. Test hook, no reference counterpart. */
+enum {
+  AG_KAT_EXP = 0,          /* f64 x -> f64 agexp::exp                                          */
+  AG_KAT_EXP_FAST,         /* f64 x -> f64 agexp::exp_fast                                     */
+  AG_KAT_SIGMOID,          /* f64 z -> f64 agexp::sigmoid                                      */
+  AG_KAT_SIGMOID_FAST,     /* f64 z -> f64 agexp::sigmoid_fast                                 */
+  AG_KAT_EXP_MAIN,         /* f64 x -> {f64 agexp::exp_main, u64 exp_in_main}                  */
+  AG_KAT_EXPF_GLIBC,       /* f32 x -> f32 agexp::expf_glibc                                   */
+  AG_KAT_TORCH_EXPF,       /* f32 x -> f32 torch_expf                                          */
+  AG_KAT_TS_CTR_OF,        /* {f32 z, i32 k, i32 K} -> f32 ts_ctr_of                           */
+  AG_KAT_LOG1P,            /* f64 x -> f64 aglog1p::log1p                                      */
+  AG_KAT_LOG1P_MAIN,       /* f64 x -> {f64 aglog1p::log1p_main, u64 ok}                       */
+  AG_KAT_LOG1P_SHARED,     /* f64 x -> {f64 log1p_main_t<SharedDiv>, r = recip(1 + x); u64 bit 0
+                              ok, bit 1 div_safe(c, u), bit 2 div_safe(f, 2 + f)}              */
+  AG_KAT_DIV,              /* {f64 a, f64 b} -> {f64 div_core(a, b, recip(b)), u64 div_safe}   */
+  AG_KAT_FXB,              /* f64 v -> i64 fxb(v)       (biased by the bits of 1.5 2^52)       */
+  AG_KAT_FXB_FAST,         /* f64 v -> i64 fxb_fast(v)                                         */
+  AG_KAT_FXB_X,            /* f64 x -> i64 fxb_x(x), x = v 2^40 already formed                 */
+  AG_KAT_FX_ROUND_GRAD,    /* f64 v -> i64 LR-TS fx_round(v, 2^40)                             */
+  AG_KAT_FX_ROUND_LOSS,    /* f64 v -> i64 LR-TS fx_round(v, 2^32)                             */
+  AG_KAT_POLAR,            /* {f64 u, f64 s} -> f64 the polar draw's transform                 */
+  AG_KAT_LR_BCE,           /* {f32 p, i32 y} -> i64 fx_round(the LR-TS BCE term, 2^32)         */
+  AG_KAT_SOFTPLUS_FAST,    /* f64 u -> {f64 softplus_fast, f64 e}                              */
+  AG_KAT_WR_ROW,           /* f64 z -> {f64 p, f64 Lz} of the win-rate fit's y = 0 row at logit z */
+  AG_KAT_COUNT
+};
+int ag_math_kat(int32_t device, int32_t fn, const void *in, int64_t n, void *out);
+
 /* Thread-local description of the last error. */
 const char *ag_last_error(void);
 int32_t ag_abi_version(void);

@@ -52,7 +52,7 @@ static double fl_log1p(double x) {
       if (ax < 0x3c900000) return x;
       return x - x * x * 0.5;
     }
-    if (hx > 0 || hx <= (int32_t)0xbfd2bec4) { /* sqrt(2)/2- <= 1 + x < sqrt(2)+ */
+    if (hx > 0 || hx <= (int32_t)0xbfd2bec3) { /* sqrt(2)/2- <= 1 + x < sqrt(2)+ */
       k = 0;
       f = x;
       hu = 1;

@@ -1899,14 +1899,16 @@ def test_per_call_lrts_estimate_matches_oracle_forward(gpu, oracle):
     (src/BidderAllocation.py:67-68, src/Models.py:28-33) as torch computes it on the golden
     fixtures' machine (tests/test_oracle_golden.py::test_ts_forward_matches_torch pins it
     there) -- bit for bit: item counts with and without a remainder after the sgemv's 4-row
-    blocks, the Thompson draw and the MAP forward, posteriors of several widths (q). Not
+    blocks, and from 32 items on whole 32-element chunks through torch.sigmoid's vectorised exp with
+    the rest on its scalar path (K in {32, 33, 40, 64}: ag_plugin.hip's ts_ctr on both sides of
+    K & ~31), the Thompson draw and the MAP forward, posteriors of several widths (q). Not
     compared with the box's own torch: MKL's sgemv summation order depends on the host CPU
     (this box's AMD EPYC sums in order; the Intel host that ran the reference here does not)."""
     import torch
     from auctiongym_amd.BidderAllocation import PyTorchLogisticRegressionAllocator
     L = oracle.lib()
     g = np.random.default_rng(8)
-    for K in (1, 2, 3, 5, 7, 11, 12):
+    for K in (1, 2, 3, 5, 7, 11, 12, 32, 33, 40, 64):
         torch.manual_seed(K)
         al = PyTorchLogisticRegressionAllocator(None, 4, K)
         rm = al.response_model

@@ -27,6 +27,9 @@ Instantiations reached (csrc/ag_sim_p.hip, ag_lrts.hip, ag_plugin.hip):
   * k_lrts_train<DO>: DO in {1, 2, 3, 7, 8} (with 5 elsewhere: 4 and 6 are left out), one and
     several workgroups per agent; ag_estimate_ctr at widths 2 and 8; the generator at E in {1, 16}
     and noise tiles of K * (OE + 1) = 21 floats.
+  * LR-TS populations at K in {32, 33, 40, 63, 64, 65}: torch.sigmoid's vectorised 32-element chunks
+    against its scalar tail (ts_ctr_of) and the sgemv blocks against their remainder rows, per-agent
+    item counts on both sides of 32; generate mode's refusal of these shapes.
 
 Shapes the library refuses by design are asserted in test_refused_shapes, never skipped.
 """
@@ -194,9 +197,10 @@ def _population(pop, N):
     return ak, bk, init, modes
 
 
-def _general_setup(seed, N, P, K, E, OE, mech, pop, sample=True, ragged=False, B=549, catalogue=None):
+def _general_setup(seed, N, P, K, E, OE, mech, pop, sample=True, ragged=False, B=549, catalogue=None, num_items=None):
     """Engine + host inputs + the oracle's answer for a general population of any shape. catalogue:
-    (items, values) to use instead of the suite's recipe (the generator's draws stay the same)."""
+    (items, values) to use instead of the suite's recipe (the generator's draws stay the same);
+    num_items: the agents' own item counts [N] (instead of ragged's random ones)."""
     from auctiongym_amd.engine import AuctionEngine
     g = np.random.default_rng(seed)
     Do = OE + 1
@@ -211,6 +215,8 @@ def _general_setup(seed, N, P, K, E, OE, mech, pop, sample=True, ragged=False, B
     ni = g.integers(1, K + 1, N).astype(np.int32) if ragged else None
     if ragged:
         ni[0] = K
+    if num_items is not None:
+        ni, ragged = np.asarray(num_items, np.int32), True
     ctx, part, u = _rounds(g, N, P, E, B)
     more = {}
     if sample:
@@ -696,6 +702,62 @@ def test_generated_noise_tiles_and_moments(gpu):
     pe = big["policy_eps"].cpu().numpy().astype(np.float64)
     n = pe.size
     assert n >= 200_000 and abs(pe.mean()) < 5 / np.sqrt(n) and abs(pe.var() - 1) < 5 * np.sqrt(2 / n)
+    eng.close()
+
+
+# ---------------------------------------------------------------- LR-TS agents with 32 and more items
+# torch.sigmoid runs whole 32-element chunks of the K CTRs through its vectorised exp and the rest
+# through the scalar one (ts_ctr_of: k < (K & ~31) torch_expf, else expf_glibc), and the Do = 5 logits
+# change order at K & ~3: K in {32, 33, 40, 64, 65} puts items on both sides of both splits, K = 63
+# has its chunk split (32) away from every other multiple of 16. (K, OE, Thompson sampling, per-agent
+# item counts or None, seed): the seeds are ones at which the oracle's choices land on both sides of
+# every split the case has (asserted below, so a change of the recipe cannot quietly lose that)
+WIDE_LRTS = [(32, 4, True, None, 14000), (33, 4, True, None, 14010), (40, 4, True, None, 14020),
+             (64, 4, True, None, 14030), (65, 4, True, None, 14043), (63, 4, True, None, 14050),
+             (40, 2, True, None, 14060), (33, 4, False, None, 14070), (64, 4, False, None, 14080),
+             (40, 4, True, (31, 32, 33, 40), 14096), (40, 4, False, (31, 32, 33, 40), 14131)]
+WIDE_LRTS_MAX_K = 65  # the largest LR-TS catalogue the suite runs (PARITY.md)
+
+
+@pytest.mark.parametrize("K,OE,sample,counts,seed", WIDE_LRTS,
+                         ids=[f"K{c[0]}_OE{c[1]}" + ("" if c[2] else "_map") + ("_counts" if c[3] else "") for c in WIDE_LRTS])
+def test_lrts_catalogues_of_32_and_more_items(gpu, oracle, K, OE, sample, counts, seed):
+    """LR-TS allocators with truthful bidders (N = 4, P = 2, E = 5, B = 2 * 256 + 37) at K >= 32: the
+    vectorised-chunk / scalar split of the CTRs' exp and the sgemv block / remainder split of the
+    logits (OE = 4; OE = 2 sums in order), with Thompson draws and as MAP estimates, and with the
+    agents' own item counts (31, 32, 33, 40) inside K = 40 -- the splits follow the agent's count,
+    not K. Every output and the exact counter limbs equal the oracle's, under the library's own
+    kernel choice and under AG_SIM_KERNEL_GENERIC."""
+    assert max(c[0] for c in WIDE_LRTS) == WIDE_LRTS_MAX_K
+    B = 2 * 256 + 37
+    eng, (ctx, part, u, more), orc, _ = _general_setup(seed, 4, 2, K, 5, OE, K % 2, "ts", sample, B=B, num_items=counts)
+    want = orc(oracle)
+    it = want["item"]
+    if counts:  # every agent stays inside its own count; the agent of 33 items chooses its one scalar-path item
+        assert (it < np.asarray(counts)[part]).all()
+        assert (it[part == 2] == 32).any() and (it[part == 3] >= 32).any() and (it[part == 0] >= 28).any()
+    elif K & 31:  # items on both sides of the chunk split (and of the sgemv remainder, where K has one) are chosen
+        assert (it >= (K & ~31)).sum() >= 5 and (it < (K & ~31)).any() and (K % 4 == 0 or (it >= (K & ~3)).sum() >= 5)
+    inp = _upload(eng, ctx, part, u, **more)
+    _compare(*_simulate(eng, inp, B), want, f"LR-TS K={K} OE={OE} sample={sample} counts={counts} auto")
+    eng.set_simulate_kernel(True)
+    _compare(*_simulate(eng, inp, B), want, f"LR-TS K={K} OE={OE} sample={sample} counts={counts} generic")
+    eng.close()
+
+
+@pytest.mark.parametrize("K", [32, 33, 40, 64, 65])
+def test_generate_mode_refuses_32_and_more_items(gpu, K):
+    """Generate mode builds the shipped shape's screened item search alone (K <= 16): an LR-TS
+    population at K >= 32 is refused, with the limit in the message, not run some other way."""
+    from auctiongym_amd.engine import AuctionEngine
+    g = np.random.default_rng(14100 + K)
+    eng = AuctionEngine(4, 2, K, 5, 4, 1, 1.0)
+    eng.set_agent_params(np.ones(4, np.int32), np.zeros(4, np.int32))
+    eng.load_catalog(*_catalogue(g, 4, K, 5))
+    eng.load_lrts(g.normal(0, 1, (4, K, 5)).astype(np.float32), np.ones((4, K, 5), np.float32))
+    with pytest.raises(NotImplementedError, match=r"ag_simulate_generated: general populations in the shipped shape "
+                                                  r"only \(E = 5, OE = 4, K <= 16, .*P=2 D=6\)"):
+        eng.simulate_generated(0, 0, eng.alloc_outputs(64))
     eng.close()
 
 
